@@ -14,15 +14,30 @@ coder.  --steps 20 therefore times 640 frames after 96 warm-up frames.  All
 input frames are resident in HBM before the timed region.  --content noise
 / static run SURVEY.md §8(d)'s stress and best cases instead of band4.
 
-Every frame is verified (bit_exact in the line): each frame's GPU-precoded
-feed is copied out of its staging slot as it is retired (the only checking
-work inside the timed region), and after timing it is arithmetic-coded on
-host threads into the frame's stream record, whose FNV-1a-64 is compared with
-tests/golden/stream_<config>_q<q>_r<R>.json (the oracle's per-frame record
-hashes of the same band4 stream, made by tests/golden/make_stream_golden.py).
-The end-to-end leg's payloads are checked the same way.
+A plain run (--gpus 1 --steps N --warmup W) does only what the headline
+figure needs: it makes the frames resident, warms up, times the N steps,
+writes --dump-outputs if asked, and prints the line.  Each frame's
+GPU-precoded feed is copied out of its staging slot into host memory as the
+frame is retired, inside the timed region (the hand-over a caller of the hot
+path makes; --no-verify drops it).  The resident frames are capped at
+POOL_BYTES of HBM: a longer run cycles them, so set-up time and memory do not
+grow with --steps.
 
-Other legs (rank 0, N = 1), outside the timed region:
+--dump-outputs DIR writes what the timed context handed over in its last
+timed step (the frames of the last launch: block tables and feeds) as
+DIR/<name>.npy, float32 / float64, at most DUMP_BYTES in all (dump_outputs).
+The inputs are the same from run to run, so two builds can be compared
+array for array.
+
+--full adds everything else the bench measures and checks, outside the timed
+region.  Every frame is verified (bit_exact in the line): after timing each
+kept feed is arithmetic-coded on host threads into the frame's stream record,
+whose FNV-1a-64 is compared with tests/golden/stream_<config>_q<q>_r<R>.json
+(the oracle's per-frame record hashes of the same band4 stream, made by
+tests/golden/make_stream_golden.py).  The end-to-end leg's payloads are
+checked the same way.
+
+Other legs of --full (rank 0, N = 1):
   end_to_end  hot path + host entropy on native worker threads (cairo_stream)
   api_encode  evx1_encoder::encode() through the drop-in C++ API, called by a
               C++ program built against include/evx1.h (one frame per call,
@@ -77,6 +92,11 @@ def parse():
     p.add_argument("--steps", type=int, default=20, help="timed steps (engine launches of the default batch)")
     p.add_argument("--warmup", type=int, default=3, help="untimed steps before (frame 0 is the I-frame)")
     p.add_argument("--config", default="4k", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="also run the other legs (end-to-end, host-RGB, encode() API, CPU baseline) and check every "
+                        "frame against the golden stream; a plain run only times the hot path")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the outputs of the last timed step (block tables, feeds) as DIR/<name>.npy")
     p.add_argument("--cpu-frames", type=int, default=0,
                    help="P-frames in the bounded CPU baseline sample (0 = about 60 Mpixels: 10-30 s of one core)")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -103,13 +123,21 @@ def parse():
                         "case) or static (band4 frame 0 repeated: the best case)")
     p.add_argument("--no-verify", action="store_true",
                    help="skip the per-frame check of every timed frame (no feed copies in the timed region)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # Frames of one content kind resident in HBM: band4 is a distinct frame per
 # index (the golden stream); noise cycles a pool of distinct random frames
 # (consecutive frames stay uncorrelated); static is one frame.
 NOISE_POOL = 64
+# HBM for resident frames: the 1440 4K frames of the golden stream (the default
+# --full run needs 1376).  A longer stream cycles them (frame f is frame
+# f % pool), so set-up time and memory stay bounded whatever --steps asks for.
+POOL_BYTES = 1440 * 3840 * 2160 * 3
+DUMP_BYTES = 60 << 20  # --dump-outputs: bytes of .npy data in all
 
 
 def content_frame(kind: str, w: int, h: int, t: int) -> np.ndarray:
@@ -124,9 +152,56 @@ def content_frame(kind: str, w: int, h: int, t: int) -> np.ndarray:
     return rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
 
 
-def content_pool(kind: str, frames: int) -> int:
-    """Distinct resident frames needed for a stream of `frames` frames."""
-    return {"band4": frames, "noise": min(frames, NOISE_POOL), "static": 1}[kind]
+def content_pool(kind: str, frames: int, frame_bytes: int = 0) -> int:
+    """Distinct resident frames needed for a stream of `frames` frames (of
+    `frame_bytes` each: at most POOL_BYTES in all)."""
+    cap = max(8, POOL_BYTES // frame_bytes) if frame_bytes else frames
+    return {"band4": min(frames, cap), "noise": min(frames, NOISE_POOL), "static": 1}[kind]
+
+
+TABLE_COLUMNS = ("block_type", "prediction_target", "motion_x", "motion_y", "sp_pred", "sp_amount", "sp_index",
+                 "q_index", "variance")
+
+
+def dump_outputs(path: str, last: dict, limit: int = DUMP_BYTES) -> dict:
+    """Write the outputs of the last timed step as .npy files under `path`.
+    last = {frame: (block table, feed words or None, feed bits, feed status)}:
+    what Context.wait() handed over for each frame of the step.
+      frame_index.npy  (k,)         float64  stream index of each dumped frame
+      block_table.npy  (k, mbs, 9)  float32  TABLE_COLUMNS of every macroblock
+      feed_words.npy   (k, words)   float64  the feed's uint32 words, zero-padded to the longest
+      feed_bits.npy    (k,)         float64
+      feed_status.npy  (k,)         float64  FEED_VALID / FEED_OVERFLOW (then no words)
+    All frames of the step when they fit `limit` bytes, else a fixed seeded
+    sample of them (a single frame larger than the limit keeps a prefix of
+    its feed).  Every value is exact in its float type."""
+    os.makedirs(path, exist_ok=True)
+    frames = sorted(last)
+    mbs = last[frames[0]][0].size
+    words = max((0 if last[f][1] is None else last[f][1].size) for f in frames)
+    fixed = mbs * len(TABLE_COLUMNS) * 4 + 3 * 8
+    if fixed + words * 8 > limit:
+        words = max(0, (limit - fixed) // 8)
+    k = max(1, min(len(frames), limit // (fixed + words * 8)))
+    if k < len(frames):
+        pick = np.random.default_rng(1234).choice(len(frames), k, replace=False)
+        frames = [frames[i] for i in sorted(pick)]
+    table = np.zeros((k, mbs, len(TABLE_COLUMNS)), np.float32)
+    feed = np.zeros((k, words), np.float64)
+    for i, f in enumerate(frames):
+        tb, fw = last[f][0], last[f][1]
+        for c, name in enumerate(TABLE_COLUMNS):
+            table[i, :, c] = tb[name]
+        if fw is not None:
+            n = min(words, fw.size)
+            feed[i, :n] = fw[:n]
+    arrays = {"frame_index": np.array(frames, np.float64), "block_table": table, "feed_words": feed,
+              "feed_bits": np.array([last[f][2] for f in frames], np.float64),
+              "feed_status": np.array([last[f][3] for f in frames], np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {"dir": path, "frames": len(frames), "of": len(last), "bytes": int(sum(x.nbytes for x in arrays.values())),
+            "arrays": sorted(arrays)}
 
 
 class Arena:
@@ -421,8 +496,9 @@ def main():
     # the end-to-end leg encodes twice the timed frames after the same warm-up:
     # every frame of every leg is a distinct resident frame of one stream, the
     # one the golden hashes describe (4K: 1376 frames, 34 GB of HBM)
-    stream_frames = warm_frames + (timed_frames if a.no_end_to_end else 2 * timed_frames)
-    pool_n = content_pool(a.content, max(nframes, stream_frames))
+    do_e2e = a.full and not a.no_end_to_end
+    stream_frames = warm_frames + (2 * timed_frames if do_e2e else timed_frames)
+    pool_n = content_pool(a.content, max(nframes, stream_frames), w * h * 3)
     # synthetic input, generated on host threads and uploaded to HBM before timing
     frames = torch.empty((pool_n, h, w, 3), dtype=torch.uint8, device=torch.device("cuda", local))
     chunk = 16
@@ -456,20 +532,27 @@ def main():
     # the oracle's live sample (rank 0, N = 1): the CPU baseline's frames;
     # without a golden file (noise, static) also every frame of the first
     # launch and the head of the second
-    check = rank == 0 and world == 1 and not a.no_cpu_baseline
+    check = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
     golden = golden_stream(a.config, a.content, q, ring)
     # CPU baseline: frame 0 + a bounded sample of P-frames (about 60 Mpixels)
     cpu_pframes = a.cpu_frames or max(2, min(48, int(60e6 / (w * h))))
     n_check = (cpu_pframes + 1 if golden else max(cpu_pframes + 1, batch + 3)) if check else 0
     n_check = min(n_check, warm_frames)
-    verify = not a.no_verify
+    hand_over = not a.no_verify  # every feed copied to host memory as its frame is retired
+    verify = a.full and hand_over  # and checked after timing
     hot = FrameStore()
+    dump_from = nframes - batch if a.dump_outputs and rank == 0 else nframes  # the last timed step's frames
+    last = {}
 
     def keep(f, out, ticket):
-        hot.keep_feed(cairo_amd, ctx, f, out, ticket)
+        if hand_over or f < n_check:
+            hot.keep_feed(cairo_amd, ctx, f, out, ticket)
+        if f >= dump_from:
+            last[f] = (out.table.copy(), None if out.feed is None else out.feed.copy(), out.feed_bits,
+                       out.feed_status)
 
     # warmup: frame 0 (I) + P-frames, in the same context and launches as the timed region
-    run_hot_path(ctx, frame_ptr, 0, warm_frames, q, stages, keep if verify or n_check else None)
+    run_hot_path(ctx, frame_ptr, 0, warm_frames, q, stages, keep if hand_over or n_check else None)
     ctx.sync()
     hot.reserve_for(timed_frames)
     note(rank, "warm-up done")
@@ -477,10 +560,12 @@ def main():
     ctx.take_timings()
     barrier()
     t0 = time.perf_counter()
-    run_hot_path(ctx, frame_ptr, warm_frames, timed_frames, q, stages, keep if verify else None)
+    run_hot_path(ctx, frame_ptr, warm_frames, timed_frames, q, stages,
+                 keep if hand_over or dump_from < nframes else None)
     ctx.sync()
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(a.dump_outputs, last) if last else None
     intervals = ctx.busy_intervals()
     kernel_ms, kframes = ctx.take_timings()
     launches = max(1, a.steps)
@@ -546,7 +631,7 @@ def main():
 
     e2e = None
     e2e_store = FrameStore() if verify else None
-    if not a.no_end_to_end:
+    if do_e2e:
         note(rank, "end-to-end leg")
         # the pipeline's depth: two launches in flight hold 2 * batch staging
         # slots, the host entropy works on the rest; 128 (not the library's
@@ -560,7 +645,7 @@ def main():
         ctx2.close()
     ctx.close()
     host_leg = None
-    if not a.no_host_rgb and world == 1:
+    if a.full and not a.no_host_rgb and world == 1:
         note(rank, "host-RGB leg")
         host_leg = host_rgb(cairo_amd, a, w, h, ring, q, batch, local)
     single = None
@@ -572,7 +657,7 @@ def main():
     torch.cuda.empty_cache()
 
     api = None
-    if rank == 0 and world == 1 and not a.no_api:
+    if a.full and rank == 0 and world == 1 and not a.no_api:
         note(rank, "encode() API leg")
         api = api_encode(w, h, ring, q, 2 + max(4, min(12, int(100e6 / (w * h)))))
 
@@ -585,6 +670,7 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": head["ms_per_step"],
         "higher_is_better": True,
         "scaling": head["scaling"],
@@ -613,6 +699,7 @@ def main():
         "host_rgb": host_leg,
         "api_encode": api,
         "single_stream": single,
+        "dumped_outputs": dumped,
     }
     exact = None
     if verify or n_check:
@@ -701,8 +788,9 @@ def single_stream(cairo_amd, frame_ptr, a, w, h, ring, q, batch, warm, timed, ba
     rank k encodes frames n = k (mod N), reading the other ranks'
     reconstructions, output_cache and progress words in place over xGMI
     (IPC handles exchanged over gloo).  Strong scaling: the same frames as
-    the N = 1 run, value = stream pixels / max-over-ranks time.  The first
-    frames are serialized and compared with the oracle on rank 0.  Failures
+    the N = 1 run, value = stream pixels / max-over-ranks time.  With --full
+    every member's frames are checked against the golden hashes and the first
+    frames against the oracle on rank 0.  Failures
     are reported, not raised (the replicas line above stays valid)."""
     import torch
 
@@ -770,7 +858,7 @@ def single_stream(cairo_amd, frame_ptr, a, w, h, ring, q, batch, warm, timed, ba
     # this member's frames, checked after the timed region: the live oracle's
     # first frames on rank 0 below, every frame against the golden hashes
     mine = {}
-    if not err:
+    if not err and a.full:
         mine = frame_hashes(cairo_amd, store, w, h, ring, q, max(1, host_cpus() // world))
     del store
     golden = golden_stream(a.config, a.content, q, ring)
@@ -802,7 +890,7 @@ def single_stream(cairo_amd, frame_ptr, a, w, h, ring, q, batch, warm, timed, ba
            "member_ms_per_own_frame": per_member,
            "note": "one stream, frame n on rank n % N (frame-interleaved group; each frame's reconstruction "
                    "pushed into the memory of the members that read it); same frames as the N = 1 run"}
-    if rank == 0:
+    if rank == 0 and a.full:
         from oracle import oracle as orc
 
         got = {}

@@ -14,7 +14,7 @@ for i in $(seq 1 $N); do
     read -r v h <<< "$spec"
     cp variants/ab/$v.so cairo_amd/_lib/libcairo_amd.so
     L=gpurun_out/abs_${C}_${v}_${h}_$i.log
-    timeout -k 10 300 python -u bench.py --config $C --no-cpu-baseline --no-end-to-end --no-api --no-host-rgb --helpers $h > $L 2>&1
+    timeout -k 10 300 python -u bench.py --full --config $C --no-cpu-baseline --no-end-to-end --no-api --no-host-rgb --helpers $h > $L 2>&1
     echo "$v $h $i $(tail -1 $L | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["bit_exact"])')"
   done
 done

@@ -8,4 +8,4 @@ mkdir -p $D
 cp cairo_amd/_lib/libcairo_amd.so gpurun_out/.host_saved.so
 trap 'cp gpurun_out/.host_saved.so cairo_amd/_lib/libcairo_amd.so' EXIT
 cp variants/ab/$V.so cairo_amd/_lib/libcairo_amd.so
-timeout -k 10 400 python -u bench.py --no-cpu-baseline "$@" > $D/bench_$V.json 2> $D/bench_$V.err
+timeout -k 10 400 python -u bench.py --full --no-cpu-baseline "$@" > $D/bench_$V.json 2> $D/bench_$V.err
