@@ -112,7 +112,7 @@ enum TimeoutKind : int32_t {
 #ifndef CAIRO_ACCT
 #define CAIRO_ACCT 0
 #endif
-constexpr int kAcctShards = 64, kAcctWords = 40;
+constexpr int kAcctShards = 64, kAcctWords = 44;
 struct Acct {
   // row coders
   static constexpr int kCoderTasks = 0, kCoderTotal = 1, kCoderGroupWait = 2, kCoderWindow = 3, kCoderSearch = 4,
@@ -140,6 +140,10 @@ struct Acct {
   // above; to the first barrier), the filters, the write-out (stores, drain,
   // progress word)
   static constexpr int kDbInputs = 37, kDbFilter = 38, kDbWrite = 39;
+  // the intra search's evaluation passes (one barrier each): their sum over
+  // the macroblocks, and the macroblocks whose stages 1-4 took 2, 3 and 4
+  // passes (stage 0 always takes one more)
+  static constexpr int kSrchPasses = 40, kSrchPasses2 = 41, kSrchPasses3 = 42, kSrchPasses4 = 43;
 };
 
 // Frames per engine launch.

@@ -770,6 +770,51 @@ __device__ __forceinline__ void select_int(Sel& s, bool valid, int cx, int cy, i
   }
 }
 
+// Two integer steps in one replay: row 0 (lanes 0..15) holds the candidates of
+// a step and row 1 (lanes 16..31) those the next step has if the first keeps
+// the state.  Both rows fold against the same state with select_int's keys
+// (each row in its own mode); the second row's winner counts only if the
+// first row had none, which is when the sequential loop would have evaluated
+// exactly these candidates from exactly this state.  Returns true if the
+// second step was consumed (`two`, wave-uniform: row 1 holds one).
+__device__ __forceinline__ bool select_int2(Sel& s, bool two, bool valid, int cx, int cy, int sad, int mad,
+                                            int px, int py, int thr, int lane) {
+  const int c = lane & 15;
+  const bool live = lane < (two ? 32 : 16) && valid;
+  const int ssd = (cx - px) * (cx - px) + (cy - py) * (cy - py);
+  const uint32_t fm2 = (uint32_t)__ballot(live && mad < thr);
+  const uint32_t fm0 = fm2 & 0xFFFFu, fm1 = fm2 >> 16;
+  const bool copy = s.mad < thr;
+  const uint32_t fmr = lane < 16 ? fm0 : fm1;  // this lane's row
+  const int f = copy || !fmr ? -1 : (int)__builtin_ctz(fmr);
+  uint32_t key = 0xFFFFFFFFu;
+  if (live) key = copy || fmr ? (c >= f ? key_copy(mad, ssd, c + 1) : 0xFFFFFFFFu) : key_sad(sad, ssd, c + 1);
+  key = min(key, (uint32_t)__builtin_amdgcn_mov_dpp((int)key, 0x128, 0xF, 0xF, false));
+  key = min(key, (uint32_t)__builtin_amdgcn_mov_dpp((int)key, 0x124, 0xF, 0xF, false));
+  key = min(key, (uint32_t)__builtin_amdgcn_mov_dpp((int)key, 0x122, 0xF, 0xF, false));
+  key = min(key, (uint32_t)__builtin_amdgcn_mov_dpp((int)key, 0x121, 0xF, 0xF, false));
+  const uint32_t kc = key_copy(s.mad, s.ssd, 0), ks = key_sad(s.sad, s.ssd, 0);
+  auto winner = [&](uint32_t k, uint32_t fm) -> int {  // -1 = keep the state
+    if (!copy && fm) return (int)(k & 15) - 1;  // the first candidate below thr is always in the running
+    return k < (copy ? kc : ks) ? (int)(k & 15) - 1 : -1;
+  };
+  int w = winner((uint32_t)__builtin_amdgcn_readlane((int)key, 0), fm0);
+  bool second = false;
+  if (two && w < 0) {
+    second = true;
+    w = winner((uint32_t)__builtin_amdgcn_readlane((int)key, 16), fm1);
+    if (w >= 0) w += 16;
+  }
+  if (w >= 0) {
+    s.bx = __builtin_amdgcn_readlane(cx, w);
+    s.by = __builtin_amdgcn_readlane(cy, w);
+    s.sad = __builtin_amdgcn_readlane(sad, w);
+    s.ssd = __builtin_amdgcn_readlane(ssd, w);
+    s.mad = __builtin_amdgcn_readlane(mad, w);
+  }
+  return second;
+}
+
 // Sub-pel step: candidate c = 2*n + q (neighbour n, q = quarter).
 __device__ __forceinline__ void select_sub(Sel& s, bool valid, int sad, int mad, int thr, int lane) {
   const int c = lane & 15;
@@ -2206,41 +2251,69 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         sel.sp_idx = sel.sp_amt = sel.sp_en = 0;
         int buf = 0;
         uint64_t t_ev = 0, t_ba = 0, t_se = 0;  // (CAIRO_ACCT builds: the stages' phases)
+        int passes = 0;  // (CAIRO_ACCT builds: evaluation passes of this macroblock)
+        // Evaluation passes.  Stage 0 is a pass of its own:
+        // groups 0..8 evaluate its 9 candidates.  A stage k >= 1 has 8: its
+        // centre is the state re-evaluated, which no (strict) acceptance rule
+        // takes.  Groups 0..7 evaluate them, and groups 8..15 the 8 candidates
+        // stage k+1 has if stage k keeps its centre.  One replay behind the
+        // pass's barrier folds both (select_int2): when stage k leaves the
+        // state where it was, stage k+1's winner from entries 8..15 counts too
+        // and the loop advances two stages; otherwise they are dropped (the
+        // next pass writes the other buffer).  The state is wave-uniform and
+        // the same in every wave, so is the decision.
   #pragma unroll 1
-        for (int stage = 0; stage < ((CAIRO_ATTR_SKIP & 16) ? 0 : 5); stage++) {
+        for (int stage = 0; stage < ((CAIRO_ATTR_SKIP & 16) ? 0 : 5);) {
           const int step = stage == 0 ? kRadius : (kRadius >> stage);
           const int jlo = stage == 0 ? -2 * kRadius : -step;
+          const int n0 = stage == 0 ? 9 : 8;              // candidates of this stage
+          const bool spec = stage >= 1 && stage < 4;      // the second half speculates stage + 1
           const int bx0 = sel.bx, by0 = sel.by;
           const uint64_t ts0 = acct_now();
-          if (grp < 9) {  // group g < 9 evaluates candidate g; groups 9..15 idle (7/16 of the work saved)
-            const int c = min(grp, 8);
-            const int cx = bx0 - step + (c % 3) * step, cy = by0 + jlo + (c / 3) * step;
-            const bool ok = intra_valid(cx, cy, px, py, ap->wa, ap->ha);
-            int sad, mad;
-            cand_row(L.win, oy, cx, ok ? cy : py - 48, gi, s, thr, sad, mad);
-            if (gi == 0 && grp < 9) {
-              L.cand[buf][grp][0] = ok ? sad : -1;
-              L.cand[buf][grp][1] = mad;
+          {
+            const bool second = stage >= 1 && grp >= 8;
+            const int c = second ? grp - 8 : grp;
+            const int k9 = stage == 0 || c < 4 ? c : c + 1;  // skip the centre of the 3x3
+            const int st = second ? step >> 1 : step;
+            if (second ? spec : grp < n0) {
+              const int cx = bx0 - st + (k9 % 3) * st, cy = by0 + (second ? -st : jlo) + (k9 / 3) * st;
+              const bool ok = intra_valid(cx, cy, px, py, ap->wa, ap->ha);
+              int sad, mad;
+              cand_row(L.win, oy, cx, ok ? cy : py - 48, gi, s, thr, sad, mad);
+              if (gi == 0) {
+                L.cand[buf][grp][0] = ok ? sad : -1;
+                L.cand[buf][grp][1] = mad;
+              }
             }
           }
           const uint64_t ts1 = acct_now();
           __syncthreads();
           const uint64_t ts2 = acct_now();
           {
+            // lanes 0..15: this stage's entries; lanes 16..23: entries 8..15, stage + 1 if the centre stays
             const int c = lane & 15;
-            const int vs = L.cand[buf][c][0], vm = L.cand[buf][c][1];
-            const int cx = bx0 - step + (c % 3) * step, cy = by0 + jlo + (c / 3) * step;
-            select_int(sel, c < 9 && vs >= 0, cx, cy, vs, vm, px, py, thr, lane);
+            const bool row1 = (lane & 16) != 0;
+            const int e = row1 ? 8 + (c & 7) : c;
+            const int vs = L.cand[buf][e][0], vm = L.cand[buf][e][1];
+            const int k9 = stage == 0 || c < 4 ? c : c + 1;
+            const int st = row1 ? step >> 1 : step;
+            const int cx = bx0 - st + (k9 % 3) * st, cy = by0 + (row1 ? -st : jlo) + (k9 / 3) * st;
+            stage += select_int2(sel, spec, c < (row1 ? 8 : n0) && vs >= 0, cx, cy, vs, vm, px, py, thr, lane) ? 2 : 1;
           }
           buf ^= 1;
           if (CAIRO_ACCT) {
             const uint64_t ts3 = uni((int)sel.bx) == -99999 ? 0 : acct_now();  // after the replay's result
             t_ev += ts1 - ts0, t_ba += ts2 - ts1, t_se += ts3 - ts2;
+            passes++;
           }
         }
         acct_add(ap->acct, Acct::kSrchEval, t_ev);
         acct_add(ap->acct, Acct::kSrchBarrier, t_ba);
         acct_add(ap->acct, Acct::kSrchSelect, t_se);
+        if (CAIRO_ACCT && passes >= 3) {  // stage 0's pass, then 2..4 for stages 1-4
+          acct_add(ap->acct, Acct::kSrchPasses, (uint64_t)passes);
+          acct_add(ap->acct, Acct::kSrchPasses2 + (passes - 3), 1);
+        }
         stamp(*ap, mb, 3);
         if (!(CAIRO_ATTR_SKIP & 16)) {  // sub-pel (perform_intra_subpixel_motion_search, motion.cpp:277-317)
           const int bx0 = sel.bx, by0 = sel.by;

@@ -69,6 +69,10 @@ def main():
     coder["search_phases"] = {k: round(us(c[k]) / mbs, 3) for k in
                               ("search_eval", "search_barrier", "search_select", "subpel_eval", "subpel_barrier",
                                "subpel_select")}
+    # evaluation passes (one barrier each) per macroblock: stage 0's, then 2..4 for stages 1-4 (5 = no
+    # speculated stage was ever reused), and the share of macroblocks at each count
+    coder["search_passes"] = {"per_mb": round(c["search_passes"] / mbs, 3)}
+    coder["search_passes"].update({k: round(c["search_mbs_" + k] / mbs, 4) for k in ("2pass", "3pass", "4pass")})
     helper = {k: round(us(c["helper_" + k]) / groups, 3) for k in ("total", "wait", "deblock", "search", "catchup")}
     helper["rest"] = round(helper["total"] - sum(helper[k] for k in ("wait", "deblock", "search", "catchup")), 3)
     helper["dequeue_per_task"] = round(us(c["helper_dequeue"]) / max(c["helper_tasks"], 1), 2)
