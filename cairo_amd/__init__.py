@@ -36,7 +36,7 @@ BLOCK_DESC = np.dtype(
 assert BLOCK_DESC.itemsize == 16
 
 EVX_SUCCESS = 0
-API_VERSION = 3  # include/cairo_amd.h CAIRO_AMD_API_VERSION
+API_VERSION = 4  # include/cairo_amd.h CAIRO_AMD_API_VERSION
 OUT_COEF, OUT_FEED = 1, 2  # cairo_ctx_set_outputs
 FEED_NONE, FEED_VALID, FEED_OVERFLOW = 0, 1, 2
 MAX_COEF_CHUNKS = 16  # CAIRO_MAX_COEF_CHUNKS
@@ -46,6 +46,10 @@ PEEK_SOURCE, PEEK_PREDICTION, PEEK_BLOCK_TABLE, PEEK_QUANT_TABLE, PEEK_SPMP_TABL
     PEEK_DESTINATION = range(7)
 MAX_BATCH = 48  # kMaxBatch (kernels.h CAIRO_MAX_BATCH): frames per engine launch, stamp layout
 EVX_ERROR_HARDWAREFAIL = 5
+EVX_ERROR_INVALID_ARGS = 1
+# Pixel formats (include/cairo_amd.h CAIRO_FMT_*): a frame is one contiguous
+# uint8 buffer with a row pitch in bytes (0: tight); see frame_layout.
+FMT_RGB24, FMT_BGR24, FMT_I420, FMT_NV12 = range(4)
 
 
 # In-kernel wait kinds of a timeout record (include/cairo_amd.h CAIRO_WAIT_*)
@@ -84,6 +88,13 @@ def lib() -> ctypes.CDLL:
         "cairo_ctx_destroy": (I, [P]),
         "cairo_ctx_reset": (I, [P]),
         "cairo_ctx_submit": (I, [P, P, I, U, U, U, ctypes.POINTER(I)]),
+        "cairo_ctx_submit_fmt": (I, [P, P, I, I, U, U, U, U, ctypes.POINTER(I)]),
+        "cairo_ctx_decode_frame_fmt": (I, [P, P, P, U, I, U, P]),
+        "cairo_frame_layout": (I, [I, U, U, U, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(U)]),
+        "cairo_kat_convert": (I, [I, I, U, U, U, P, P, P, P, I]),
+        "cairo_stream_submit_fmt": (I, [P, P, I, I, U, U, U, U, ctypes.POINTER(I)]),
+        "evx_encoder_set_input_format": (I, [P, I, U]),
+        "evx_decoder_set_output_format": (I, [P, I, U]),
         "cairo_ctx_wait": (I, [P, I, P]),
         "cairo_ctx_release": (I, [P, I]),
         "cairo_ctx_sync": (I, [P]),
@@ -184,6 +195,56 @@ def _host_frame(rgb, width: int, height: int) -> int:
     return rgb.ctypes.data
 
 
+def frame_layout(fmt: int, w: int, h: int, pitch: int = 0):
+    """-> (bytes of a w x h frame of format fmt with row pitch `pitch`, its
+    tight pitch); pitch 0 means tight (cairo_frame_layout).  ValueError for an
+    unknown format, an odd or zero size, a pitch below the tight one, or an
+    odd I420 pitch.  No device needed."""
+    nb, tight = ctypes.c_uint64(), ctypes.c_uint32()
+    ok = all(isinstance(x, (int, np.integer)) and 0 <= x < 2 ** 32 for x in (w, h, pitch)) and \
+        isinstance(fmt, (int, np.integer)) and -2 ** 31 <= fmt < 2 ** 31
+    if not ok or lib().cairo_frame_layout(int(fmt), int(w), int(h), int(pitch), ctypes.byref(nb), ctypes.byref(tight)):
+        raise ValueError(f"no frame layout for format {fmt}, {w}x{h}, pitch {pitch}")
+    return nb.value, tight.value
+
+
+def split_frame(buf: np.ndarray, fmt: int, w: int, h: int, pitch: int = 0):
+    """Plane views of a frame buffer: (y, u, v) for I420, (y, uv) for NV12
+    (uv: (h/2, w/2, 2)), the (h, w, 3) pixels for the RGB formats; each view
+    covers the image only, not the pitch padding."""
+    nb, tight = frame_layout(fmt, w, h, pitch)
+    p = pitch or tight
+    b = np.asarray(buf).reshape(-1)
+    if b.dtype != np.uint8 or b.size != nb:
+        raise ValueError(f"a format {fmt} frame of {w}x{h}, pitch {p} is {nb} uint8, got {b.dtype} x {b.size}")
+    if fmt in (FMT_RGB24, FMT_BGR24):
+        return b.reshape(h, p)[:, :3 * w].reshape(h, w, 3) if p == tight else \
+            np.lib.stride_tricks.as_strided(b, (h, w, 3), (p, 3, 1))
+    y = b[:p * h].reshape(h, p)[:, :w]
+    if fmt == FMT_I420:
+        cp, ch = p // 2, h // 2
+        u = b[p * h:p * h + cp * ch].reshape(ch, cp)[:, :w // 2]
+        v = b[p * h + cp * ch:p * h + 2 * cp * ch].reshape(ch, cp)[:, :w // 2]
+        return y, u, v
+    uv = b[p * h:].reshape(h // 2, p)[:, :w].reshape(h // 2, w // 2, 2)
+    return y, uv
+
+
+def _host_frame_fmt(frame, fmt: int, width: int, height: int, pitch: int) -> int:
+    """Address of a host frame of any format, after checking dtype, contiguity
+    and that it holds exactly frame_layout's bytes (the native side copies
+    that many from it asynchronously).  (RGB24, 0) is _host_frame."""
+    if fmt == FMT_RGB24 and not pitch:
+        return _host_frame(frame, width, height)
+    nb, _ = frame_layout(fmt, width, height, pitch)
+    if not isinstance(frame, np.ndarray):
+        raise TypeError("host frames are numpy arrays (pass on_device=True for a device address)")
+    if frame.dtype != np.uint8 or frame.nbytes != nb or not frame.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"a format {fmt} frame of {width}x{height}, pitch {pitch} must be a C-contiguous uint8 "
+                         f"array of {nb} bytes, got {frame.dtype} {frame.shape}")
+    return frame.ctypes.data
+
+
 def make_band4(w: int, h: int, t: int, seed: int = 1234) -> np.ndarray:
     """band4 synthetic RGB888 frame, shape (h, w, 3)."""
     out = np.empty((h, w, 3), np.uint8)
@@ -256,13 +317,20 @@ class Context:
     def stages(self) -> int:
         return int(self.L.cairo_ctx_stages(self.h))
 
-    def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False) -> int:
+    def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
+               fmt: int = FMT_RGB24, pitch: int = 0) -> int:
+        """fmt / pitch: the frame's layout (FMT_*, row pitch in bytes, 0:
+        tight); the defaults are today's tight RGB888 through cairo_ctx_submit."""
         t = ctypes.c_int()
-        ptr = rgb if on_device else _host_frame(rgb, self.width, self.height)
-        _ck(
-            self.L.cairo_ctx_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
-            "cairo_ctx_submit",
-        )
+        ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, self.width, self.height, pitch)
+        if fmt == FMT_RGB24 and not pitch:
+            _ck(
+                self.L.cairo_ctx_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
+                "cairo_ctx_submit",
+            )
+        else:
+            _ck(self.L.cairo_ctx_submit_fmt(self.h, ptr, int(on_device), fmt, pitch, index, int(inter), quality,
+                                            ctypes.byref(t)), "cairo_ctx_submit_fmt")
         if not on_device:  # the H2D copy is asynchronous: keep the host frame alive
             self._keep[t.value] = rgb
         return t.value
@@ -340,8 +408,9 @@ class Context:
     def release(self, ticket: int) -> None:
         _ck(self.L.cairo_ctx_release(self.h, ticket), "cairo_ctx_release")
 
-    def encode_frame(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False) -> FrameOutputs:
-        t = self.submit(rgb, index, inter, quality, on_device)
+    def encode_frame(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
+                     fmt: int = FMT_RGB24, pitch: int = 0) -> FrameOutputs:
+        t = self.submit(rgb, index, inter, quality, on_device, fmt=fmt, pitch=pitch)
         try:
             return self.wait(t, copy=True)
         finally:
@@ -510,9 +579,10 @@ class Group:
         self._join()
         self.tickets = {}
 
-    def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False) -> None:
+    def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
+               fmt: int = FMT_RGB24, pitch: int = 0) -> None:
         m = self.members[index % self.size]
-        self.tickets[index] = m.submit(rgb, index, inter, quality, on_device)
+        self.tickets[index] = m.submit(rgb, index, inter, quality, on_device, fmt=fmt, pitch=pitch)
 
     def wait(self, index: int, copy: bool = True) -> FrameOutputs:
         """Outputs of frame `index`; launches every member's pending frames first
@@ -637,11 +707,16 @@ class Stream:
         self.h = p
         self._keep = {}
 
-    def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False) -> int:
+    def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
+               fmt: int = FMT_RGB24, pitch: int = 0) -> int:
         t = ctypes.c_int()
-        ptr = rgb if on_device else _host_frame(rgb, self.ctx.width, self.ctx.height)
-        _ck(self.L.cairo_stream_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
-            "cairo_stream_submit")
+        ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, self.ctx.width, self.ctx.height, pitch)
+        if fmt == FMT_RGB24 and not pitch:
+            _ck(self.L.cairo_stream_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
+                "cairo_stream_submit")
+        else:
+            _ck(self.L.cairo_stream_submit_fmt(self.h, ptr, int(on_device), fmt, pitch, index, int(inter), quality,
+                                               ctypes.byref(t)), "cairo_stream_submit_fmt")
         if not on_device:
             self._keep[t.value] = rgb
         return t.value
@@ -745,7 +820,27 @@ class Encoder:
     def clear(self) -> None:
         _ck(self.L.evx_encoder_clear(self.h), "clear")
 
-    def encode(self, rgb: np.ndarray, bs: BitStream) -> None:
+    def set_input_format(self, fmt: int, pitch: int = 0) -> None:
+        """The layout encode() reads its frames in from now on (FMT_*, row pitch
+        in bytes, 0: tight); callable between frames.  peek() stays RGB888."""
+        _ck(self.L.evx_encoder_set_input_format(self.h, fmt, pitch), "set_input_format")
+        self._fmt, self._pitch = fmt, pitch
+
+    def encode(self, rgb: np.ndarray, bs: BitStream, width: int | None = None, height: int | None = None) -> None:
+        """Encode one frame.  With the default input format, rgb is (height,
+        width, 3) RGB888.  After set_input_format, it is a uint8 buffer of
+        frame_layout(fmt, width, height, pitch) bytes; width and height may be
+        left out where the array's shape is (height, width, 3)."""
+        fmt, pitch = getattr(self, "_fmt", FMT_RGB24), getattr(self, "_pitch", 0)
+        if fmt != FMT_RGB24 or pitch:
+            if width is None or height is None:
+                if not isinstance(rgb, np.ndarray) or rgb.ndim != 3 or rgb.shape[2] != 3:
+                    raise ValueError("width and height are needed for a frame that is not shaped (height, width, 3)")
+                height, width = rgb.shape[:2]
+            ptr = _host_frame_fmt(rgb, fmt, width, height, pitch)
+            _ck(self.L.evx_encoder_encode(self.h, ptr, width, height, bs.h), "encode")
+            self._shape = (width, height)
+            return
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError(f"frame must have shape (height, width, 3), got {rgb.shape}")
         h, w = rgb.shape[:2]
@@ -788,10 +883,27 @@ class Decoder:
         if device:
             _ck(self.L.evx_decoder_set_device(self.h, device), "set_device")
 
-    def decode(self, bs: "BitStream", width: int, height: int) -> np.ndarray:
-        """Decode [header +] one frame record of bs (emptied afterwards) -> RGB (h, w, 3)."""
-        out = np.zeros((height, width, 3), np.uint8)
+    def set_output_format(self, fmt: int, pitch: int = 0) -> None:
+        """The layout decode() returns its frames in from now on (FMT_*, row
+        pitch in bytes, 0: tight); callable between frames."""
+        _ck(self.L.evx_decoder_set_output_format(self.h, fmt, pitch), "set_output_format")
+        self._fmt, self._pitch = fmt, pitch
+
+    def decode(self, bs: "BitStream", width: int, height: int, out: np.ndarray | None = None) -> np.ndarray:
+        """Decode [header +] one frame record of bs (emptied afterwards) -> RGB
+        (h, w, 3) for tight RGB24 / BGR24; for a YUV or pitched output format a
+        flat uint8 buffer of frame_layout bytes (split_frame gives its planes).
+        out: a buffer to write into (its pitch padding keeps its bytes)."""
+        fmt, pitch = getattr(self, "_fmt", FMT_RGB24), getattr(self, "_pitch", 0)
+        nb, tight = frame_layout(fmt, width, height, pitch)
+        if out is None:
+            out = np.zeros(nb, np.uint8)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.nbytes != nb or \
+                not out.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"out must be a C-contiguous uint8 array of {nb} bytes")
         _ck(self.L.evx_decoder_decode(self.h, bs.h, _ptr(out)), "decode")
+        if fmt in (FMT_RGB24, FMT_BGR24) and (not pitch or pitch == tight):
+            return out.reshape(height, width, 3)
         return out
 
     def clear(self) -> None:

@@ -205,6 +205,11 @@ struct cairo_ctx {
   uint32_t epoch = 0;
   int batch_max = 16;
   FrameDesc pend[kMaxBatch];
+  // Layout of each pending frame as the convert kernel reads it (CAIRO_FMT_*,
+  // row pitch in bytes): a device frame's own, a staged host frame's tight
+  // one.  pend_hpitch: the pitch of a host source still to upload (flush).
+  uint8_t pend_fmt[kMaxBatch] = {};
+  uint32_t pend_pitch[kMaxBatch] = {}, pend_hpitch[kMaxBatch] = {};
   int npend = 0;
   int last_slot = -1;  // slot of the last launched frame
   uint32_t last_epoch = 0;  // and its epoch (the tag of its inter records)
@@ -508,6 +513,31 @@ int collect_times(cairo_ctx* c, TimedBatch& t) {
   return kSuccess;
 }
 
+// Upload a host frame of format fmt into a staging slot, packed tight: one
+// copy when the source is tight (pitch 0 or the tight pitch), else a 2D copy
+// per plane.  Every tight format fits the slot's 3 * w * h bytes.
+int upload_frame(const cairo_ctx* c, uint8_t* dst, const uint8_t* src, int fmt, uint32_t pitch, hipStream_t st) {
+  uint64_t bytes = 0;
+  uint32_t tight = 0;
+  if (cairo_frame_layout(fmt, c->w, c->h, 0, &bytes, &tight) != kSuccess) return kInvalidArg;
+  if (!pitch || pitch == tight) {
+    CK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, st));
+    return kSuccess;
+  }
+  const size_t w = c->w, h = c->h;
+  CK(hipMemcpy2DAsync(dst, tight, src, pitch, tight, h, hipMemcpyHostToDevice, st));  // RGB rows, or the Y plane
+  const uint8_t* sc = src + (size_t)pitch * h;
+  uint8_t* dc = dst + w * h;
+  if (fmt == CAIRO_FMT_I420) {
+    const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
+    CK(hipMemcpy2DAsync(dc, cw, sc, cp, cw, ch, hipMemcpyHostToDevice, st));
+    CK(hipMemcpy2DAsync(dc + cw * ch, cw, sc + cp * ch, cp, cw, ch, hipMemcpyHostToDevice, st));
+  } else if (fmt == CAIRO_FMT_NV12) {
+    CK(hipMemcpy2DAsync(dc, w, sc, pitch, w, h / 2, hipMemcpyHostToDevice, st));
+  }
+  return kSuccess;
+}
+
 // Launch the pending batch.
 int flush(cairo_ctx* c) {
   if (c->npend == 0) return kSuccess;
@@ -583,8 +613,10 @@ int flush(cairo_ctx* c) {
   }
   for (int i = 0; i < e.nframes; i++) {  // host RGB sources; the decoder's table and coefficients
     const FrameDesc& f = c->pend[i];
-    if (f.host_rgb)
-      CK(hipMemcpyAsync((void*)f.rgb, f.host_rgb, (size_t)c->w * c->h * 3, hipMemcpyHostToDevice, st));
+    if (f.host_rgb) {
+      const int r = upload_frame(c, const_cast<uint8_t*>(f.rgb), f.host_rgb, c->pend_fmt[i], c->pend_hpitch[i], st);
+      if (r) return r;
+    }
     if (f.decode) {
       CK(hipMemcpyAsync(c->table + (size_t)f.slot * c->mbs, f.host_table, c->mbs * sizeof(BlockDesc),
                         hipMemcpyHostToDevice, st));
@@ -611,9 +643,23 @@ int flush(cairo_ctx* c) {
                       hipMemcpyHostToDevice, st));
   }
   if (tb) CK(hipEventRecord(tb->ev[0], st));
-  CK(launch_convert_batch(ca, st));
+  // A launch of tight RGB24 frames keeps k_convert_batch, whose behaviour
+  // beside the running launch is measured; any other
+  // layout in the launch takes all of its frames through k_convert_fmt_batch.
+  bool tight_rgb = true;
+  for (int i = 0; i < e.nframes; i++)
+    tight_rgb &= !ca.rgb[i] || (c->pend_fmt[i] == CAIRO_FMT_RGB24 && c->pend_pitch[i] == 3 * c->w);
+  if (tight_rgb) {
+    CK(launch_convert_batch(ca, st));
+  } else {
+    ConvertFmtArgs cf{};
+    cf.c = ca;
+    for (int i = 0; i < e.nframes; i++) cf.fmt[i] = c->pend_fmt[i], cf.pitch[i] = c->pend_pitch[i];
+    CK(launch_convert_fmt_batch(cf, st));
+  }
   CK(hipEventRecord(c->fdesc_done[fslot], st));  // fh has been read
   c->fdesc_used[fslot] = true;
+  // (a staged frame of any format starts at its slot's address)
   for (int i = 0; i < e.nframes; i++) {  // staged host RGB converted: the buffer may be refilled
     const FrameDesc& f = c->pend[i];
     Stage& s = c->st[f.slot];
@@ -1046,9 +1092,14 @@ int cairo_ctx_busy_intervals(cairo_ctx* c, double* out, int cap, int* n) {
   return kSuccess;
 }
 
-int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32_t index,
-                     uint32_t type, uint32_t quality, int* ticket) {
+// cairo_ctx_submit (RGB24, tight) and cairo_ctx_submit_fmt.  check_range: an
+// on-device frame must lie, with all its bytes, inside one allocation.
+static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch, bool check_range,
+                        uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (!c || !rgb || !ticket || quality < 1 || quality > 31 || type > 1) return kInvalidArg;
+  uint64_t frame_bytes = 0;
+  uint32_t tight = 0;
+  if (cairo_frame_layout(fmt, c->w, c->h, pitch, &frame_bytes, &tight) != kSuccess) return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
   CK(hipSetDevice(c->device));
   const int t = c->next_ticket;
@@ -1066,8 +1117,22 @@ int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32
               c->device);
       return kInvalidArg;
     }
+    if (check_range) {  // a wrong pitch is refused here, not found as a read past the buffer
+      hipDeviceptr_t base = nullptr;
+      size_t size = 0;
+      if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)rgb) != hipSuccess ||
+          (uint64_t)((const uint8_t*)rgb - (const uint8_t*)base) + frame_bytes > (uint64_t)size) {
+        (void)hipGetLastError();
+        fprintf(stderr, "[cairo_amd] submit: a format %d frame with pitch %u (%llu bytes) at %p does not fit its allocation\n",
+                fmt, pitch ? pitch : tight, (unsigned long long)frame_bytes, (const void*)rgb);
+        return kInvalidArg;
+      }
+    }
   }
   FrameDesc& f = c->pend[c->npend];
+  c->pend_fmt[c->npend] = (uint8_t)fmt;
+  c->pend_pitch[c->npend] = rgb_on_device && pitch ? pitch : tight;  // a host frame is staged tight
+  c->pend_hpitch[c->npend] = pitch;
   if (rgb_on_device) {
     f.rgb = rgb;
     f.host_rgb = nullptr;
@@ -1096,7 +1161,10 @@ int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32
         CK(hipStreamWaitEvent(up, s.rgb_read, 0));
         s.rgb_pending = false;
       }
-      CK(hipMemcpyAsync((void*)f.rgb, rgb, (size_t)c->w * c->h * 3, hipMemcpyHostToDevice, up));
+      {  // packed tight into the slot, frame_bytes long (3 * w * h for RGB24)
+        const int ru = upload_frame(c, const_cast<uint8_t*>(f.rgb), rgb, fmt, pitch, up);
+        if (ru) return ru;
+      }
       CK(hipEventRecord(c->up_last, up));
       c->up_pending = true;
       f.host_rgb = nullptr;
@@ -1129,6 +1197,16 @@ int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32
   *ticket = t;
   if (c->npend >= c->batch_max) return flush(c);
   return kSuccess;
+}
+
+int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32_t index,
+                     uint32_t type, uint32_t quality, int* ticket) {
+  return submit_frame(c, rgb, rgb_on_device, CAIRO_FMT_RGB24, 0, false, index, type, quality, ticket);
+}
+
+int cairo_ctx_submit_fmt(cairo_ctx* c, const uint8_t* frame, int on_device, int fmt, uint32_t pitch, uint32_t index,
+                         uint32_t type, uint32_t quality, int* ticket) {
+  return submit_frame(c, frame, on_device, fmt, pitch, true, index, type, quality, ticket);
 }
 
 static const char* timeout_kind_name(int k) {
@@ -1248,9 +1326,16 @@ int cairo_ctx_wait(cairo_ctx* c, int ticket, cairo_frame_result* out) {
   return frame_result(c, s, out);
 }
 
-int cairo_ctx_decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index,
-                           uint8_t* rgb) {
+// cairo_ctx_decode_frame (fmt < 0: RGB888 through k_yuv_to_rgb, as ever) and
+// cairo_ctx_decode_frame_fmt (k_planes_to_fmt, tight in the staging slot; the
+// D2H copy is 2D per plane when the caller's frame is pitched).
+static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, int fmt,
+                        uint32_t pitch, uint8_t* rgb) {
   if (!c || !table || !coef || !rgb) return kInvalidArg;
+  uint64_t frame_bytes = (uint64_t)c->w * c->h * 3;
+  uint32_t tight = 3 * c->w;
+  if (fmt >= 0 && cairo_frame_layout(fmt, c->w, c->h, pitch, nullptr, &tight) != kSuccess) return kInvalidArg;
+  if (fmt >= 0) (void)cairo_frame_layout(fmt, c->w, c->h, 0, &frame_bytes, nullptr);  // as staged: tight
   std::lock_guard<std::mutex> lk(c->mu);
   if (c->gsize > 1) return kInvalidResource;
   CK(hipSetDevice(c->device));
@@ -1286,13 +1371,32 @@ int cairo_ctx_decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* co
   if (r == kSuccess) {
     hipStream_t st = (b & 1) ? c->ks2 : c->ks;
     uint8_t* drgb = c->rgb + (size_t)slot * c->w * c->h * 3;
-    r = fail(launch_yuv_to_rgb(slot_planes(c->ring_buf, c, (int)(index % c->ring)), (int)c->wa, (int)c->w,
-                               (int)c->h, drgb, st), "launch_yuv_to_rgb");
+    const PlaneSet recon = slot_planes(c->ring_buf, c, (int)(index % c->ring));
+    if (fmt < 0)
+      r = fail(launch_yuv_to_rgb(recon, (int)c->wa, (int)c->w, (int)c->h, drgb, st), "launch_yuv_to_rgb");
+    else
+      r = fail(launch_planes_to_fmt(recon, (int)c->wa, (int)c->w, (int)c->h, fmt, tight, drgb, st),
+               "launch_planes_to_fmt");
     if (r == kSuccess)
       r = fail(hipMemcpyAsync(s.err, c->sticky, TimeoutInfo::kWords * sizeof(int32_t), hipMemcpyDeviceToHost, st),
                "hipMemcpyAsync");
-    if (r == kSuccess)
-      r = fail(hipMemcpyAsync(rgb, drgb, (size_t)c->w * c->h * 3, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    if (r == kSuccess && (fmt < 0 || !pitch || pitch == tight)) {
+      r = fail(hipMemcpyAsync(rgb, drgb, (size_t)frame_bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    } else if (r == kSuccess) {  // row by row: the caller's pitch padding keeps its bytes
+      const size_t w = c->w, h = c->h;
+      r = fail(hipMemcpy2DAsync(rgb, pitch, drgb, tight, tight, h, hipMemcpyDeviceToHost, st), "hipMemcpy2DAsync");
+      uint8_t* dc = rgb + (size_t)pitch * h;
+      const uint8_t* sc = drgb + w * h;
+      if (r == kSuccess && fmt == CAIRO_FMT_I420) {
+        const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
+        r = fail(hipMemcpy2DAsync(dc, cp, sc, cw, cw, ch, hipMemcpyDeviceToHost, st), "hipMemcpy2DAsync");
+        if (r == kSuccess)
+          r = fail(hipMemcpy2DAsync(dc + cp * ch, cp, sc + cw * ch, cw, cw, ch, hipMemcpyDeviceToHost, st),
+                   "hipMemcpy2DAsync");
+      } else if (r == kSuccess && fmt == CAIRO_FMT_NV12) {
+        r = fail(hipMemcpy2DAsync(dc, pitch, sc, w, w, h / 2, hipMemcpyDeviceToHost, st), "hipMemcpy2DAsync");
+      }
+    }
     if (r == kSuccess) r = fail(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (r == kSuccess && s.err[TimeoutInfo::kKind]) {
       report_timeout_host(c, s.err, index, st);  // (mu held: the launch stream, idle now)
@@ -1301,6 +1405,17 @@ int cairo_ctx_decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* co
   }
   s.busy = false;
   return r;
+}
+
+int cairo_ctx_decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index,
+                           uint8_t* rgb) {
+  return decode_frame(c, table, coef, index, -1, 0, rgb);
+}
+
+int cairo_ctx_decode_frame_fmt(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, int fmt,
+                               uint32_t pitch, uint8_t* out) {
+  if (fmt < 0) return kInvalidArg;
+  return decode_frame(c, table, coef, index, fmt, pitch, out);
 }
 
 int cairo_ctx_max_workgroups(const cairo_ctx* c) { return c ? c->max_rows : 0; }

@@ -70,8 +70,10 @@ class gpu_decoder : public evx1_decoder {
       return EVX_ERROR_EXECUTION_FAILURE;
     input->set_read_index(rd);
     if (!valid_table()) return EVX_ERROR_EXECUTION_FAILURE;
-    if (cairo_ctx_decode_frame(ctx_, reinterpret_cast<const uint8_t *>(table_), coef_, f.index,
-                               static_cast<uint8_t *>(output)))
+    const uint8_t *tbl = reinterpret_cast<const uint8_t *>(table_);
+    if (fmt_ == CAIRO_FMT_RGB24 && !pitch_
+            ? cairo_ctx_decode_frame(ctx_, tbl, coef_, f.index, static_cast<uint8_t *>(output))
+            : cairo_ctx_decode_frame_fmt(ctx_, tbl, coef_, f.index, fmt_, pitch_, static_cast<uint8_t *>(output)))
       return EVX_ERROR_EXECUTION_FAILURE;
     frame_index_++;
     input->empty();
@@ -81,6 +83,15 @@ class gpu_decoder : public evx1_decoder {
   evx_status set_device(int device) {
     if (initialized_) return EVX_ERROR_INVALIDARG;
     device_ = device;
+    return EVX_SUCCESS;
+  }
+  // The layout decode() writes its frame in (between frames too).
+  evx_status set_output_format(int fmt, uint32 pitch) {
+    // before the first decode the frame size is not known: any even size stands in
+    const uint32 w = initialized_ ? width_ : 2, h = initialized_ ? height_ : 2;
+    if (cairo_frame_layout(fmt, w, h, initialized_ ? pitch : 0, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
+    fmt_ = fmt;
+    pitch_ = pitch;
     return EVX_SUCCESS;
   }
 
@@ -158,6 +169,8 @@ class gpu_decoder : public evx1_decoder {
   uint32 frame_index_;
   uint32 width_ = 0, height_ = 0, wa_ = 0, ha_ = 0, wmb_ = 0, hmb_ = 0, ring_ = 0;
   int device_ = 0;
+  int fmt_ = CAIRO_FMT_RGB24;  // output layout (set_output_format)
+  uint32 pitch_ = 0;
   cairo_ctx *ctx_ = nullptr;
   cairo::BlockDesc *table_ = nullptr;
   int16 *coef_ = nullptr;
@@ -192,6 +205,9 @@ int evx_decoder_decode(void *dec, void *bs, void *rgb) {
 }
 int evx_decoder_set_device(void *dec, int device) {
   return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_device(device);
+}
+int evx_decoder_set_output_format(void *dec, int fmt, uint32_t pitch) {
+  return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_output_format(fmt, pitch);
 }
 
 }  // extern "C"

@@ -79,13 +79,17 @@ class gpu_encoder : public evx1_encoder {
       if (evx_failed(output->write_bytes(&h, sizeof(h)))) return EVX_ERROR_EXECUTION_FAILURE;
     }
     if (width != width_ || height != height_) return EVX_ERROR_INVALID_RESOURCE;
+    if (cairo_frame_layout(fmt_, width, height, pitch_, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
     frame_t f = frame_;
     if (evx_failed(output->write_bytes(&f, sizeof(f)))) return EVX_ERROR_EXECUTION_FAILURE;
 
     const auto t0 = std::chrono::steady_clock::now();
     int ticket = -1;
-    int r = cairo_ctx_submit(ctx_, (const uint8_t *)image, 0, frame_.index, frame_.type,
-                             frame_.quality, &ticket);
+    int r = fmt_ == CAIRO_FMT_RGB24 && !pitch_
+                ? cairo_ctx_submit(ctx_, (const uint8_t *)image, 0, frame_.index, frame_.type, frame_.quality,
+                                   &ticket)
+                : cairo_ctx_submit_fmt(ctx_, (const uint8_t *)image, 0, fmt_, pitch_, frame_.index, frame_.type,
+                                       frame_.quality, &ticket);
     if (r) return EVX_ERROR_EXECUTION_FAILURE;
     cairo_frame_result res;
     r = cairo_ctx_wait(ctx_, ticket, &res);
@@ -190,6 +194,15 @@ class gpu_encoder : public evx1_encoder {
     device_ = device;
     return EVX_SUCCESS;
   }
+  // The layout encode() reads its image in (between frames too).
+  evx_status set_input_format(int fmt, uint32 pitch) {
+    // before the first encode the frame size is not known: any even size stands in
+    const uint32 w = initialized_ ? width_ : 2, h = initialized_ ? height_ : 2;
+    if (cairo_frame_layout(fmt, w, h, initialized_ ? pitch : 0, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
+    fmt_ = fmt;
+    pitch_ = pitch;
+    return EVX_SUCCESS;
+  }
 
  private:
   void reset_frame() {  // clear_frame, common.cpp:50-65
@@ -219,6 +232,8 @@ class gpu_encoder : public evx1_encoder {
   uint32 width_ = 0, height_ = 0;
   uint32 ring_ = kDefaultRing;
   int device_ = 0;
+  int fmt_ = CAIRO_FMT_RGB24;  // input layout (set_input_format)
+  uint32 pitch_ = 0;
   cairo_ctx *ctx_ = nullptr;
   uint8 *last_table_ = nullptr;
 };
@@ -260,6 +275,9 @@ int evx_encoder_set_ring(void *enc, uint32_t ring) {
 }
 int evx_encoder_set_device(void *enc, int device) {
   return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_device(device);
+}
+int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch) {
+  return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_format(fmt, pitch);
 }
 
 // band4 generator: deterministic synthetic content.

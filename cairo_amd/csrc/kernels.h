@@ -363,6 +363,20 @@ struct ConvertArgs {
 // RGB -> YUV of every frame of the batch into its slot's source planes, plus
 // the views and sync area above (grid slice z = nframes).
 hipError_t launch_convert_batch(const ConvertArgs& c, hipStream_t s);
+// The same launch when any of its frames is not tight RGB24 (pixfmt.hip):
+// every frame carries its format (CAIRO_FMT_*) and row pitch in bytes, and is
+// read in place at any byte alignment.  c.wa is the pitch of the planes.
+struct ConvertFmtArgs {
+  ConvertArgs c;
+  uint32_t pitch[kMaxBatch];
+  uint8_t fmt[kMaxBatch];
+};
+hipError_t launch_convert_fmt_batch(const ConvertFmtArgs& c, hipStream_t s);
+// Plane set src (rows of plane_pitch elements) as a w x h frame of format fmt
+// with the given row pitch (bytes) at dst; bytes outside the image's rows are
+// not written.
+hipError_t launch_planes_to_fmt(PlaneSet src, int plane_pitch, int w, int h, int fmt, uint32_t pitch, uint8_t* dst,
+                                hipStream_t s);
 // The pipelined encode engine: inter search, macroblock rows (intra search,
 // classify, transform, quantize, reconstruct) and in-loop deblock.
 hipError_t launch_engine(const EngineArgs& e, hipStream_t s);

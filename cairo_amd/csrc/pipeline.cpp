@@ -230,8 +230,9 @@ int cairo_stream_create(cairo_ctx* ctx, int threads, cairo_stream** out) {
   return kSuccess;
 }
 
-int cairo_stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, uint32_t index,
-                        uint32_t type, uint32_t quality, int* ticket) {
+// cairo_stream_submit (fmt < 0: cairo_ctx_submit) and cairo_stream_submit_fmt.
+static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch,
+                         uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (!s || !rgb || !ticket) return kInvalidArg;
   const int t = s->next;
   {
@@ -246,7 +247,8 @@ int cairo_stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, 
     });
   }
   int tk = -1;
-  const int r = cairo_ctx_submit(s->ctx, rgb, rgb_on_device, index, type, quality, &tk);
+  const int r = fmt < 0 ? cairo_ctx_submit(s->ctx, rgb, rgb_on_device, index, type, quality, &tk)
+                        : cairo_ctx_submit_fmt(s->ctx, rgb, rgb_on_device, fmt, pitch, index, type, quality, &tk);
   if (r) return r;
   {
     std::lock_guard<std::mutex> lk(s->m);
@@ -262,6 +264,17 @@ int cairo_stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, 
   s->next = tk + 1;
   *ticket = tk;
   return kSuccess;
+}
+
+int cairo_stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, uint32_t index,
+                        uint32_t type, uint32_t quality, int* ticket) {
+  return stream_submit(s, rgb, rgb_on_device, -1, 0, index, type, quality, ticket);
+}
+
+int cairo_stream_submit_fmt(cairo_stream* s, const uint8_t* frame, int on_device, int fmt, uint32_t pitch,
+                            uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
+  if (fmt < 0) return kInvalidArg;
+  return stream_submit(s, frame, on_device, fmt, pitch, index, type, quality, ticket);
 }
 
 int cairo_stream_collect(cairo_stream* s, int ticket, uint8_t* out, uint64_t out_bytes,

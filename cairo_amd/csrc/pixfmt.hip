@@ -1,0 +1,377 @@
+// cairo_amd/csrc/pixfmt.hip -- pixel formats at the codec's edges: BGR24,
+// I420 and NV12 frames (and RGB24 with a row pitch) into the int16 4:2:0
+// source planes, and ring-slot planes out into any of the four formats.
+//
+// The default launch (every frame tight RGB24) keeps k_convert_batch, and
+// cairo_ctx_decode_frame keeps k_yuv_to_rgb (kernels.hip): both are measured
+// beside a running engine launch.  The kernels here run
+// whenever a launch holds any other layout.
+//
+// Work split of both kernels: one thread owns a strip of 8 luma columns by 2
+// rows (4 chroma samples per plane), so that a strip's Y rows are one 16-byte
+// plane access each and its 8-bit side is whole dwords.  A strip falls back to
+// byte accesses where its row start is not aligned or where it is cut by the
+// right edge; nothing outside width x height is read or written on either
+// side, so the pitch padding of a destination keeps its bytes.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstdio>
+
+#include "../../include/cairo_amd.h"
+#include "kernels.h"
+
+namespace cairo {
+
+namespace {
+
+constexpr int kStrip = 8;         // luma columns per thread
+constexpr int kFmtThreads = 128;  // a workgroup spans 1024 luma columns of one row pair
+
+// saturate narrows to int16 first (math.h:218-221).  The result is pinned to a
+// 32-bit register of its own before it is shifted into its dword: left to
+// itself the compiler fuses shift, clamp and byte packing into
+// v_ashr_pk_u8_i32 and 16-bit ops, and bytes 2 and 3 of a packed dword then
+// carried bits of an unclamped neighbour on the device (the same source is
+// right on a CPU; the KAT's output side caught it).
+__device__ __forceinline__ uint32_t sat8(int32_t v) {
+  const int s = (int)(int16_t)v;
+  uint32_t r = (uint32_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(r));
+#endif
+  return r;
+}
+__device__ __forceinline__ uint32_t clamp8(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// Byte k of a little-endian dword array.
+template <int W>
+__device__ __forceinline__ int byte_of(const uint32_t (&w)[W], int k) {
+  return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
+}
+
+// The first n of N bytes at p (N a multiple of 4) into dwords: dword loads
+// when all N are wanted and p is 4-byte aligned, else byte loads of the n
+// valid ones (the rest read as 0).
+template <int N>
+__device__ __forceinline__ void load_bytes(const uint8_t* p, int n, uint32_t (&w)[N / 4]) {
+  if (n == N && ((uintptr_t)p & 3) == 0) {
+    const uint32_t* q = (const uint32_t*)p;
+#pragma unroll
+    for (int k = 0; k < N / 4; k++) w[k] = q[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < N / 4; k++) w[k] = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++)
+      if (k < n) w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3));
+  }
+}
+
+// The first n of N bytes held in dwords to p; bytes from n on are not written.
+template <int N>
+__device__ __forceinline__ void store_bytes(uint8_t* p, int n, const uint32_t (&w)[N / 4]) {
+  if (n == N && ((uintptr_t)p & 3) == 0) {
+    uint32_t* q = (uint32_t*)p;
+#pragma unroll
+    for (int k = 0; k < N / 4; k++) q[k] = w[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; k++)
+      if (k < n) p[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+  }
+}
+
+// The first n of N plane elements (N = 8: 16 bytes, N = 4: 8 bytes) at p as
+// one vector access when all are wanted and p is aligned to it.
+template <int N>
+__device__ __forceinline__ void store_i16(int16_t* p, int n, const int (&v)[N]) {
+  static_assert(N == 8 || N == 4, "a 16-byte or an 8-byte plane access");
+  if (n == N && ((uintptr_t)p & (2 * N - 1)) == 0) {
+    uint32_t w[N / 2];
+#pragma unroll
+    for (int k = 0; k < N / 2; k++) w[k] = ((uint32_t)v[2 * k] & 0xFFFFu) | ((uint32_t)v[2 * k + 1] << 16);
+    if constexpr (N == 8)
+      *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
+    else
+      *(uint2*)p = make_uint2(w[0], w[1]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; k++)
+      if (k < n) p[k] = (int16_t)v[k];
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void load_i16(const int16_t* p, int n, int (&v)[N]) {
+  static_assert(N == 8 || N == 4, "a 16-byte or an 8-byte plane access");
+  if (n == N && ((uintptr_t)p & (2 * N - 1)) == 0) {
+    uint32_t w[N / 2];
+    if constexpr (N == 8) {
+      const uint4 q = *(const uint4*)p;
+      w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+    } else {
+      const uint2 q = *(const uint2*)p;
+      w[0] = q.x, w[1] = q.y;
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = (int)(int16_t)(w[k >> 1] >> (16 * (k & 1)));
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = k < n ? (int)p[k] : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Input side: strip sx of row pair qy of one frame -> its source planes.
+// RGB24 / BGR24: the arithmetic of k_convert_batch (convert.cpp:11-14, 30-73).
+// I420 / NV12: the codec's own full-range BT.601 samples, Y + 16, U, V.
+// ---------------------------------------------------------------------------
+template <int FMT>
+__device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pitch, const PlaneSet& in, int w, int h,
+                                              int wa, int sx, int qy) {
+  const int x0 = sx * kStrip;
+  const int n = min(kStrip, w - x0);  // luma columns of this strip inside the image: 2, 4, 6 or 8
+  const int nc = n >> 1;
+  int yv[2][kStrip], uv[kStrip / 2], vv[kStrip / 2];
+  if constexpr (FMT == CAIRO_FMT_RGB24 || FMT == CAIRO_FMT_BGR24) {
+    int su[kStrip / 2] = {}, sv[kStrip / 2] = {};
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++) {
+      uint32_t px[6];
+      load_bytes<24>(frame + (size_t)(2 * qy + dy) * pitch + 3 * x0, 3 * n, px);
+#pragma unroll
+      for (int k = 0; k < kStrip; k++) {
+        const int c0 = byte_of(px, 3 * k), g = byte_of(px, 3 * k + 1), c2 = byte_of(px, 3 * k + 2);
+        const int r = FMT == CAIRO_FMT_RGB24 ? c0 : c2, b = FMT == CAIRO_FMT_RGB24 ? c2 : c0;
+        yv[dy][k] = ((77 * r + 150 * g + 29 * b + 128) >> 8) + 16;
+        su[k >> 1] += ((-43 * r - 85 * g + 128 * b + 128) / 256) + 128;
+        sv[k >> 1] += ((128 * r - 107 * g - 21 * b + 128) / 256) + 128;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kStrip / 2; k++) uv[k] = (su[k] + 2) >> 2, vv[k] = (sv[k] + 2) >> 2;
+  } else {
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++) {
+      uint32_t py[2];
+      load_bytes<8>(frame + (size_t)(2 * qy + dy) * pitch + x0, n, py);
+#pragma unroll
+      for (int k = 0; k < kStrip; k++) yv[dy][k] = byte_of(py, k) + 16;
+    }
+    const uint8_t* chroma = frame + (size_t)pitch * h;
+    if constexpr (FMT == CAIRO_FMT_I420) {
+      const size_t cp = pitch >> 1;
+      const uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
+      uint32_t pu[1], pv[1];
+      load_bytes<4>(up, nc, pu);
+      load_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
+#pragma unroll
+      for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(pu, k), vv[k] = byte_of(pv, k);
+    } else {
+      uint32_t puv[2];
+      load_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
+#pragma unroll
+      for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(puv, 2 * k), vv[k] = byte_of(puv, 2 * k + 1);
+    }
+  }
+#pragma unroll
+  for (int dy = 0; dy < 2; dy++) store_i16<kStrip>(in.y + (size_t)(2 * qy + dy) * wa + x0, n, yv[dy]);
+  const size_t co = (size_t)qy * (wa >> 1) + (x0 >> 1);
+  store_i16<kStrip / 2>(in.u + co, nc, uv);
+  store_i16<kStrip / 2>(in.v + co, nc, vv);
+}
+
+// Same grid convention as k_convert_batch: slice z < nframes converts frame z
+// (a null source: a decoded frame, nothing to convert), slice z == nframes
+// copies the launch's frame views to the device and zeroes its sync area.
+__global__ __launch_bounds__(kFmtThreads) void k_convert_fmt_batch(ConvertFmtArgs e) {
+  if ((int)blockIdx.z == e.c.nframes) {
+    const int nb = gridDim.x * gridDim.y, t = (blockIdx.y * gridDim.x + blockIdx.x) * kFmtThreads + threadIdx.x;
+    for (int k = t; k < e.c.fa_chunks; k += nb * kFmtThreads) e.c.fa_dev[k] = e.c.fa_host[k];
+    for (int k = t; k < e.c.sync_words; k += nb * kFmtThreads) e.c.sync[k] = 0;
+    return;
+  }
+  const uint8_t* frame = e.c.rgb[blockIdx.z];
+  const int sx = blockIdx.x * kFmtThreads + threadIdx.x, qy = blockIdx.y;
+  if (!frame || sx * kStrip >= e.c.w) return;
+  const PlaneSet in = e.c.in[blockIdx.z];
+  const uint32_t pitch = e.pitch[blockIdx.z];
+  switch (e.fmt[blockIdx.z]) {  // uniform over the workgroup
+    case CAIRO_FMT_RGB24: convert_strip<CAIRO_FMT_RGB24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
+    case CAIRO_FMT_BGR24: convert_strip<CAIRO_FMT_BGR24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
+    case CAIRO_FMT_I420: convert_strip<CAIRO_FMT_I420>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
+    default: convert_strip<CAIRO_FMT_NV12>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Output side: strip sx of row pair qy of a plane set -> the pitched frame.
+// RGB24 / BGR24: the arithmetic of k_yuv_to_rgb (convert.cpp:16-19, 162-223).
+// I420 / NV12: clamp(Y - 16), clamp(U), clamp(V) of the int16 samples.
+// ---------------------------------------------------------------------------
+template <int FMT>
+__device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w, int h, uint32_t pitch, uint8_t* dst,
+                                             int sx, int qy) {
+  const int x0 = sx * kStrip;
+  const int n = min(kStrip, w - x0);
+  const int nc = n >> 1;
+  int yv[2][kStrip], uv[kStrip / 2], vv[kStrip / 2];
+#pragma unroll
+  for (int dy = 0; dy < 2; dy++) load_i16<kStrip>(src.y + (size_t)(2 * qy + dy) * sp + x0, n, yv[dy]);
+  const size_t co = (size_t)qy * (sp >> 1) + (x0 >> 1);
+  load_i16<kStrip / 2>(src.u + co, nc, uv);
+  load_i16<kStrip / 2>(src.v + co, nc, vv);
+  if constexpr (FMT == CAIRO_FMT_RGB24 || FMT == CAIRO_FMT_BGR24) {
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++) {
+      uint32_t px[6] = {};
+#pragma unroll
+      for (int k = 0; k < kStrip; k++) {
+        const int yy = yv[dy][k] - 16, u = uv[k >> 1] - 128, v = vv[k >> 1] - 128;
+        const uint32_t r = sat8((256 * yy + 358 * v + 128) >> 8);
+        const uint32_t g = sat8((256 * yy - 88 * u - 182 * v + 128) >> 8);
+        const uint32_t b = sat8((256 * yy + 452 * u + 128) >> 8);
+        const uint32_t c0 = FMT == CAIRO_FMT_RGB24 ? r : b, c2 = FMT == CAIRO_FMT_RGB24 ? b : r;
+        px[(3 * k) >> 2] |= c0 << (8 * ((3 * k) & 3));
+        px[(3 * k + 1) >> 2] |= g << (8 * ((3 * k + 1) & 3));
+        px[(3 * k + 2) >> 2] |= c2 << (8 * ((3 * k + 2) & 3));
+      }
+      store_bytes<24>(dst + (size_t)(2 * qy + dy) * pitch + 3 * x0, 3 * n, px);
+    }
+  } else {
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++) {
+      uint32_t py[2] = {};
+#pragma unroll
+      for (int k = 0; k < kStrip; k++) py[k >> 2] |= clamp8(yv[dy][k] - 16) << (8 * (k & 3));
+      store_bytes<8>(dst + (size_t)(2 * qy + dy) * pitch + x0, n, py);
+    }
+    uint8_t* chroma = dst + (size_t)pitch * h;
+    if constexpr (FMT == CAIRO_FMT_I420) {
+      const size_t cp = pitch >> 1;
+      uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
+      uint32_t pu[1] = {}, pv[1] = {};
+#pragma unroll
+      for (int k = 0; k < kStrip / 2; k++) pu[0] |= clamp8(uv[k]) << (8 * k), pv[0] |= clamp8(vv[k]) << (8 * k);
+      store_bytes<4>(up, nc, pu);
+      store_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
+    } else {
+      uint32_t puv[2] = {};
+#pragma unroll
+      for (int k = 0; k < kStrip / 2; k++)
+        puv[k >> 1] |= (clamp8(uv[k]) | (clamp8(vv[k]) << 8)) << (16 * (k & 1));
+      store_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kFmtThreads) void k_planes_to_fmt(PlaneSet src, int sp, int w, int h, int fmt,
+                                                               uint32_t pitch, uint8_t* dst) {
+  const int sx = blockIdx.x * kFmtThreads + threadIdx.x, qy = blockIdx.y;
+  if (sx * kStrip >= w) return;
+  switch (fmt) {
+    case CAIRO_FMT_RGB24: planes_strip<CAIRO_FMT_RGB24>(src, sp, w, h, pitch, dst, sx, qy); break;
+    case CAIRO_FMT_BGR24: planes_strip<CAIRO_FMT_BGR24>(src, sp, w, h, pitch, dst, sx, qy); break;
+    case CAIRO_FMT_I420: planes_strip<CAIRO_FMT_I420>(src, sp, w, h, pitch, dst, sx, qy); break;
+    default: planes_strip<CAIRO_FMT_NV12>(src, sp, w, h, pitch, dst, sx, qy); break;
+  }
+}
+
+constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
+
+int fail(hipError_t e, const char* what) {
+  if (e == hipSuccess) return kSuccess;
+  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
+  return kHardwareFail;
+}
+
+dim3 strip_grid(int w, int h, int slices) {
+  const int strips = (w + kStrip - 1) / kStrip;
+  return dim3((strips + kFmtThreads - 1) / kFmtThreads, h / 2, slices);
+}
+
+}  // namespace
+
+hipError_t launch_convert_fmt_batch(const ConvertFmtArgs& e, hipStream_t s) {
+  hipLaunchKernelGGL(k_convert_fmt_batch, strip_grid(e.c.w, e.c.h, e.c.nframes + 1), dim3(kFmtThreads), 0, s, e);
+  return hipGetLastError();
+}
+
+hipError_t launch_planes_to_fmt(PlaneSet src, int plane_pitch, int w, int h, int fmt, uint32_t pitch, uint8_t* dst,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(k_planes_to_fmt, strip_grid(w, h, 1), dim3(kFmtThreads), 0, s, src, plane_pitch, w, h, fmt, pitch,
+                     dst);
+  return hipGetLastError();
+}
+
+}  // namespace cairo
+
+using namespace cairo;
+
+extern "C" {
+
+int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint32_t pitch, uint64_t* bytes,
+                       uint32_t* tight_pitch) {
+  if (fmt < CAIRO_FMT_RGB24 || fmt > CAIRO_FMT_NV12 || !width || !height || (width & 1) || (height & 1))
+    return kInvalidArg;
+  const bool rgb = fmt == CAIRO_FMT_RGB24 || fmt == CAIRO_FMT_BGR24;
+  const uint64_t tight = rgb ? (uint64_t)3 * width : width;
+  if (tight > 0xFFFFFFFFull) return kInvalidArg;
+  const uint64_t p = pitch ? pitch : tight;
+  if (p < tight || (fmt == CAIRO_FMT_I420 && (p & 1))) return kInvalidArg;
+  if (bytes) *bytes = rgb ? p * height : p * height + p * (height / 2);  // 4:2:0: chroma rows hold pitch bytes in all
+  if (tight_pitch) *tight_pitch = (uint32_t)tight;
+  return kSuccess;
+}
+
+int cairo_kat_convert(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, uint8_t* frame, int16_t* y, int16_t* u,
+                      int16_t* v, int device) {
+  uint64_t bytes = 0;
+  uint32_t tight = 0;
+  // (a grid's y extent is at most 65535 row pairs; column offsets are ints)
+  if (dir < 0 || dir > 1 || !frame || !y || !u || !v || w > (1u << 20) || h > 2 * 65535u ||
+      cairo_frame_layout(fmt, w, h, pitch, &bytes, &tight) != kSuccess)
+    return kInvalidArg;
+  if (!pitch) pitch = tight;
+  int r = fail(hipSetDevice(device), "hipSetDevice");
+  if (r) return r;
+  const size_t ny = (size_t)w * h, nc = (size_t)(w / 2) * (h / 2);
+  uint8_t* df = nullptr;
+  int16_t* dp = nullptr;  // y | u | v, tight: w and w / 2 elements per row
+  if ((r = fail(hipMalloc(&df, bytes), "malloc")) || (r = fail(hipMalloc(&dp, (ny + 2 * nc) * 2), "malloc"))) goto done;
+  {
+    PlaneSet p;
+    p.y = dp, p.u = dp + ny, p.v = dp + ny + nc;
+    if (dir == 0) {
+      ConvertFmtArgs a{};
+      a.c.w = (int)w, a.c.h = (int)h, a.c.wa = (int)w, a.c.nframes = 1;
+      a.c.rgb[0] = df;
+      a.c.in[0] = p;
+      a.fmt[0] = (uint8_t)fmt;
+      a.pitch[0] = pitch;
+      if ((r = fail(hipMemcpy(df, frame, bytes, hipMemcpyHostToDevice), "h2d")) ||
+          (r = fail(launch_convert_fmt_batch(a, nullptr), "k_convert_fmt_batch")) ||
+          (r = fail(hipDeviceSynchronize(), "sync")) ||
+          (r = fail(hipMemcpy(y, p.y, ny * 2, hipMemcpyDeviceToHost), "d2h")) ||
+          (r = fail(hipMemcpy(u, p.u, nc * 2, hipMemcpyDeviceToHost), "d2h")) ||
+          (r = fail(hipMemcpy(v, p.v, nc * 2, hipMemcpyDeviceToHost), "d2h")))
+        goto done;
+    } else {
+      if ((r = fail(hipMemcpy(df, frame, bytes, hipMemcpyHostToDevice), "h2d")) ||
+          (r = fail(hipMemcpy(p.y, y, ny * 2, hipMemcpyHostToDevice), "h2d")) ||
+          (r = fail(hipMemcpy(p.u, u, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
+          (r = fail(hipMemcpy(p.v, v, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
+          (r = fail(launch_planes_to_fmt(p, (int)w, (int)w, (int)h, fmt, pitch, df, nullptr), "k_planes_to_fmt")) ||
+          (r = fail(hipDeviceSynchronize(), "sync")) ||
+          (r = fail(hipMemcpy(frame, df, bytes, hipMemcpyDeviceToHost), "d2h")))
+        goto done;
+    }
+  }
+done:
+  (void)hipFree(df);
+  (void)hipFree(dp);
+  return r;
+}
+
+}  // extern "C"

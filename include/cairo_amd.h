@@ -38,11 +38,39 @@ extern "C" {
  *   1  round 3: cairo_task_queues(hmb, frames, pool, ...)
  *   2  round 4: cairo_task_queues gains n_helpers and n_rows,
  *      cairo_group_check_queues gains hw_queues
- *   3  round 5: cairo_ctx_read_inter refuses stale (untagged) records */
-#define CAIRO_AMD_API_VERSION 3
+ *   3  round 5: cairo_ctx_read_inter refuses stale (untagged) records
+ *   4  pixel formats: cairo_frame_layout, cairo_ctx_submit_fmt,
+ *      cairo_ctx_decode_frame_fmt, cairo_stream_submit_fmt, cairo_kat_convert,
+ *      evx_encoder_set_input_format, evx_decoder_set_output_format */
+#define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
 typedef struct cairo_ctx cairo_ctx;
+
+/* ---- pixel formats ---------------------------------------------------------
+ * A frame is one contiguous buffer of 8-bit samples, `pitch` bytes from one
+ * row to the next; pitch == 0 means tight (3*width for the RGB formats, width
+ * for the YUV formats).  Widths and heights are even. */
+#define CAIRO_FMT_RGB24 0  /* R,G,B bytes (today's format); pitch >= 3*width              */
+#define CAIRO_FMT_BGR24 1  /* B,G,R bytes; pitch >= 3*width                               */
+#define CAIRO_FMT_I420  2  /* Y: height rows of pitch bytes; then U: height/2 rows of     */
+                           /* pitch/2 bytes; then V likewise. pitch even, >= width        */
+#define CAIRO_FMT_NV12  3  /* Y: height rows of pitch bytes; then height/2 rows of pitch  */
+                           /* bytes of interleaved U,V (U first). pitch >= width          */
+/* BGR24 is RGB24 with the first and third byte swapped: same arithmetic, same
+ * bits.  I420 and NV12 carry the codec's own colour space, full-range BT.601
+ * (JFIF): on input the internal planes are Y8 + 16, U8, V8 with no conversion;
+ * on output Y8 = clamp(Y - 16), U8 = clamp(U), V8 = clamp(V), clamped to
+ * 0..255.  Limited-range video (Y 16..235, chroma 16..240) must be expanded
+ * to full range by the caller first: there is no range flag.
+ * Pixels outside width x height are never read; on output the bytes of a row
+ * beyond the image (the pitch padding) are never written. */
+/* Buffer size and tight pitch of a frame (no device needed).
+ * EVX_ERROR_INVALID_ARGS for an unknown format, an odd or zero size, a pitch
+ * below the tight pitch, or an odd pitch for I420.  bytes / tight_pitch may be
+ * NULL. */
+CAIRO_API int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint32_t pitch,
+                                 uint64_t *bytes, uint32_t *tight_pitch);
 
 /* Outputs a context hands to the host entropy stage (cairo_ctx_set_outputs). */
 #define CAIRO_OUT_COEF 1 /* the output_cache planes (default)                   */
@@ -93,6 +121,14 @@ CAIRO_API int cairo_ctx_reset(cairo_ctx *ctx);
  * on.  Returns a ticket. */
 CAIRO_API int cairo_ctx_submit(cairo_ctx *ctx, const uint8_t *rgb, int rgb_on_device,
                                uint32_t index, uint32_t type, uint32_t quality, int *ticket);
+/* The same for a frame of any CAIRO_FMT_* with a row pitch (0: tight).  A host
+ * frame is packed tight into the frame's staging slot on upload; a device
+ * frame is read in place, at any byte alignment, and must lie inside one
+ * allocation with all cairo_frame_layout bytes (else EVX_ERROR_INVALID_ARGS).
+ * The frames of one launch may mix formats.  (RGB24, 0) is cairo_ctx_submit. */
+CAIRO_API int cairo_ctx_submit_fmt(cairo_ctx *ctx, const uint8_t *frame, int on_device, int fmt,
+                                   uint32_t pitch, uint32_t index, uint32_t type, uint32_t quality,
+                                   int *ticket);
 /* Wait until the frame's block table and coefficients are host-visible. */
 CAIRO_API int cairo_ctx_wait(cairo_ctx *ctx, int ticket, cairo_frame_result *out);
 /* The decoder's hot path (decode_slice + deblock + convert_image,
@@ -103,6 +139,11 @@ CAIRO_API int cairo_ctx_wait(cairo_ctx *ctx, int ticket, cairo_frame_result *out
  * The descs must be valid (motion inside the frame; see decoder.cpp). */
 CAIRO_API int cairo_ctx_decode_frame(cairo_ctx *ctx, const uint8_t *block_table, const int16_t *coef,
                                      uint32_t index, uint8_t *rgb);
+/* The same, written as a frame of format fmt with row pitch `pitch` (0: tight)
+ * to host memory out (cairo_frame_layout bytes; the pitch padding keeps its
+ * bytes). */
+CAIRO_API int cairo_ctx_decode_frame_fmt(cairo_ctx *ctx, const uint8_t *block_table, const int16_t *coef,
+                                         uint32_t index, int fmt, uint32_t pitch, uint8_t *out);
 /* Hand the ticket's staging buffers back (required before ticket+stages). */
 CAIRO_API int cairo_ctx_release(cairo_ctx *ctx, int ticket);
 /* Launch any pending frames and block until all GPU work is finished. */
@@ -271,6 +312,14 @@ CAIRO_API int cairo_kat_transform(const int16_t *src, const int16_t *pred, const
                                   int count, int16_t *coef, int16_t *recon, int32_t *qvar,
                                   int device);
 
+/* Known-answer check of the pixel-format kernels on host buffers, without a
+ * context or the engine.  dir 0: frame (fmt, pitch) -> tight int16 planes (w
+ * and w/2 elements per row) through the input kernel.  dir 1: planes -> frame
+ * through the output kernel; frame's previous contents are uploaded first, so
+ * bytes the kernel must not touch can be checked. */
+CAIRO_API int cairo_kat_convert(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, uint8_t *frame,
+                                int16_t *y, int16_t *u, int16_t *v, int device);
+
 /* ---- host entropy stage (serialize_slice, serialize.cpp:319-340) ---------
  * Appends the ABAC payload of one frame to out (LSB-first bit order) at bit
  * *bit_pos, advancing it.  coef planes have pitch wa (luma) / wa/2 (chroma). */
@@ -320,6 +369,10 @@ CAIRO_API int cairo_stream_create(cairo_ctx *ctx, int threads, cairo_stream **ou
  * been collected. */
 CAIRO_API int cairo_stream_submit(cairo_stream *s, const uint8_t *rgb, int rgb_on_device,
                                   uint32_t index, uint32_t type, uint32_t quality, int *ticket);
+/* cairo_stream_submit for a frame of any format (cairo_ctx_submit_fmt). */
+CAIRO_API int cairo_stream_submit_fmt(cairo_stream *s, const uint8_t *frame, int on_device, int fmt,
+                                      uint32_t pitch, uint32_t index, uint32_t type, uint32_t quality,
+                                      int *ticket);
 /* Wait for the frame's payload and append it at bit *bit_pos of out
  * (out_bytes capacity, LSB-first; out == NULL only advances *bit_pos).  If it
  * does not fit, returns EVX_ERROR_CAPACITY_LIMIT (7) and keeps the payload:
@@ -352,6 +405,9 @@ CAIRO_API int evx_encoder_encode(void *enc, const void *rgb, uint32_t width, uin
 CAIRO_API int evx_encoder_peek(void *enc, int state, void *rgb);
 CAIRO_API int evx_encoder_set_ring(void *enc, uint32_t ring); /* before first encode */
 CAIRO_API int evx_encoder_set_device(void *enc, int device);  /* before first encode */
+/* The layout encode() reads its image in from now on (CAIRO_FMT_*, row pitch
+ * in bytes, 0: tight); callable between frames.  peek() keeps writing RGB888. */
+CAIRO_API int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch);
 
 /* ---- drop-in decoder, C view of evx1_decoder (evx1.h:97-112) ------------
  * decode() reads [header +] one frame record from bs (its read index onward),
@@ -362,6 +418,9 @@ CAIRO_API int evx_decoder_destroy(void *dec);
 CAIRO_API int evx_decoder_clear(void *dec);
 CAIRO_API int evx_decoder_decode(void *dec, void *bs, void *rgb);
 CAIRO_API int evx_decoder_set_device(void *dec, int device); /* before first decode */
+/* The layout decode() writes its frame in from now on (CAIRO_FMT_*, row pitch
+ * in bytes, 0: tight; cairo_frame_layout bytes); callable between frames. */
+CAIRO_API int evx_decoder_set_output_format(void *dec, int fmt, uint32_t pitch);
 
 /* bit_stream (reference bitstream.h:43-92) */
 CAIRO_API void *evx_bitstream_create(uint32_t size_in_bits);
