@@ -50,6 +50,8 @@ EVX_ERROR_INVALID_ARGS = 1
 # Pixel formats (include/cairo_amd.h CAIRO_FMT_*): a frame is one contiguous
 # uint8 buffer with a row pitch in bytes (0: tight); see frame_layout.
 FMT_RGB24, FMT_BGR24, FMT_I420, FMT_NV12 = range(4)
+# Per-frame metrics and kept reconstructions (include/cairo_amd.h, cairo_ctx_set_metrics)
+METRIC_SSE, METRIC_SSIM, KEEP_RECON = 1, 2, 4
 
 
 # In-kernel wait kinds of a timeout record (include/cairo_amd.h CAIRO_WAIT_*)
@@ -95,6 +97,15 @@ def lib() -> ctypes.CDLL:
         "cairo_stream_submit_fmt": (I, [P, P, I, I, U, U, U, U, ctypes.POINTER(I)]),
         "evx_encoder_set_input_format": (I, [P, I, U]),
         "evx_decoder_set_output_format": (I, [P, I, U]),
+        "cairo_frame_metrics_size": (I, []),
+        "cairo_ctx_set_metrics": (I, [P, I]),
+        "cairo_ctx_frame_metrics": (I, [P, I, P]),
+        "cairo_ctx_fetch_recon_planes": (I, [P, I, P, P, P]),
+        "cairo_ctx_fetch_recon": (I, [P, I, I, U, P]),
+        "cairo_stream_frame_metrics": (I, [P, I, P]),
+        "cairo_kat_metrics": (I, [U, U, U, P, P, P, P, P, P, P, I]),
+        "evx_encoder_set_metrics": (I, [P, I]),
+        "evx_encoder_last_metrics": (I, [P, P]),
         "cairo_ctx_wait": (I, [P, I, P]),
         "cairo_ctx_release": (I, [P, I]),
         "cairo_ctx_sync": (I, [P]),
@@ -271,6 +282,53 @@ class _FrameResult(ctypes.Structure):
     ]
 
 
+class _FrameMetrics(ctypes.Structure):
+    """cairo_frame_metrics (include/cairo_amd.h)."""
+    _fields_ = [
+        ("flags", ctypes.c_uint32),
+        ("width", ctypes.c_uint32),
+        ("height", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("sse", ctypes.c_uint64 * 3),
+        ("ssim_sum", ctypes.c_double * 3),
+        ("ssim_windows", ctypes.c_uint64 * 3),
+        ("samples", ctypes.c_uint64 * 3),
+    ]
+
+
+def psnr(sse: int, samples: int) -> float:
+    """10 log10(255^2 * samples / sse); inf at sse 0."""
+    return float("inf") if sse == 0 else 10.0 * float(np.log10(255.0 ** 2 * samples / sse))
+
+
+def _metrics_dict(m: "_FrameMetrics") -> dict:
+    """The raw fields of a cairo_frame_metrics plus psnr_y/u/v/all and
+    ssim_y/u/v (None for a metric that was not computed, or has no window)."""
+    d = {"flags": int(m.flags), "width": int(m.width), "height": int(m.height), "sse": [int(x) for x in m.sse],
+         "ssim_sum": [float(x) for x in m.ssim_sum], "ssim_windows": [int(x) for x in m.ssim_windows],
+         "samples": [int(x) for x in m.samples]}
+    has_sse, has_ssim = bool(m.flags & METRIC_SSE), bool(m.flags & METRIC_SSIM)
+    for k, n in enumerate("yuv"):
+        d[f"psnr_{n}"] = psnr(d["sse"][k], d["samples"][k]) if has_sse else None
+        d[f"ssim_{n}"] = d["ssim_sum"][k] / d["ssim_windows"][k] if has_ssim and d["ssim_windows"][k] else None
+    d["psnr_all"] = psnr(sum(d["sse"]), sum(d["samples"])) if has_sse else None
+    return d
+
+
+def kat_metrics(a, b, w: int, h: int, device: int = 0) -> dict:
+    """The metrics kernels on host planes, without a context (cairo_kat_metrics):
+    a and b are (y, u, v) int16 planes whose rows hold at least w (chroma: w / 2)
+    elements; the luma row length is the pitch, the chroma planes' half of it."""
+    planes = [np.ascontiguousarray(p, dtype=np.int16) for p in (*a, *b)]
+    pitch = planes[0].shape[1]
+    for y, u, v in (planes[:3], planes[3:]):
+        if y.shape != (h, pitch) or u.shape != (h // 2, pitch // 2) or v.shape != u.shape:
+            raise ValueError(f"planes must be ({h}, {pitch}) and ({h // 2}, {pitch // 2}), got {y.shape} {u.shape} {v.shape}")
+    m = _FrameMetrics()
+    _ck(lib().cairo_kat_metrics(w, h, pitch, *(_ptr(p) for p in planes), ctypes.byref(m), device), "cairo_kat_metrics")
+    return _metrics_dict(m)
+
+
 @dataclass
 class FrameOutputs:
     """Host copies of one frame's outputs (block table + output_cache)."""
@@ -404,6 +462,45 @@ class Context:
         return (_view(r.coef_y, np.int16, ny).reshape(self.ha, self.wa).copy(),
                 _view(r.coef_u, np.int16, nc).reshape(self.ha // 2, self.wa // 2).copy(),
                 _view(r.coef_v, np.int16, nc).reshape(self.ha // 2, self.wa // 2).copy())
+
+    def set_metrics(self, sse: bool = True, ssim: bool = True, keep_recon: bool = False, flags: int | None = None) -> None:
+        """Per-frame metrics and/or kept reconstructions for frames submitted
+        from now on (cairo_ctx_set_metrics; no frame may be in flight).  All
+        False turns them off and frees the kept plane sets.  flags: the raw
+        METRIC_* / KEEP_RECON bits instead."""
+        if flags is None:
+            flags = (METRIC_SSE if sse else 0) | (METRIC_SSIM if ssim else 0) | (KEEP_RECON if keep_recon else 0)
+        _ck(self.L.cairo_ctx_set_metrics(self.h, flags), "cairo_ctx_set_metrics")
+
+    def frame_metrics(self, ticket: int) -> dict:
+        """Metrics of a waited, unreleased frame: the raw cairo_frame_metrics
+        fields plus psnr_y/u/v/all (dB, inf at SSE 0) and ssim_y/u/v."""
+        m = _FrameMetrics()
+        _ck(self.L.cairo_ctx_frame_metrics(self.h, ticket, ctypes.byref(m)), "cairo_ctx_frame_metrics")
+        return _metrics_dict(m)
+
+    def fetch_recon_planes(self, ticket: int):
+        """(y, u, v) kept deblocked reconstruction of a waited, unreleased frame,
+        aligned int16 planes as read_planes returns them."""
+        y = np.empty((self.ha, self.wa), np.int16)
+        u = np.empty((self.ha // 2, self.wa // 2), np.int16)
+        v = np.empty_like(u)
+        _ck(self.L.cairo_ctx_fetch_recon_planes(self.h, ticket, _ptr(y), _ptr(u), _ptr(v)),
+            "cairo_ctx_fetch_recon_planes")
+        return y, u, v
+
+    def fetch_recon(self, ticket: int, fmt: int, pitch: int = 0, out: np.ndarray | None = None) -> np.ndarray:
+        """The same frame as a flat uint8 buffer of frame_layout(fmt, pitch)
+        bytes (split_frame gives its planes): what the decoder shows.  out: a
+        buffer to write into (its pitch padding keeps its bytes)."""
+        nb, _ = frame_layout(fmt, self.width, self.height, pitch)
+        if out is None:
+            out = np.zeros(nb, np.uint8)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.nbytes != nb or \
+                not out.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"out must be a C-contiguous uint8 array of {nb} bytes")
+        _ck(self.L.cairo_ctx_fetch_recon(self.h, ticket, fmt, pitch, _ptr(out)), "cairo_ctx_fetch_recon")
+        return out
 
     def release(self, ticket: int) -> None:
         _ck(self.L.cairo_ctx_release(self.h, ticket), "cairo_ctx_release")
@@ -744,6 +841,14 @@ class Stream:
         _ck(self.L.cairo_stream_payload_bits(self.h, ticket, ctypes.byref(p)), "cairo_stream_payload_bits")
         return p.value
 
+    def frame_metrics(self, ticket: int) -> dict:
+        """Metrics of a frame whose outputs the pipeline has picked up (a
+        collected frame, until ticket + 2 * stages is submitted); the context's
+        set_metrics comes before the stream is created."""
+        m = _FrameMetrics()
+        _ck(self.L.cairo_stream_frame_metrics(self.h, ticket, ctypes.byref(m)), "cairo_stream_frame_metrics")
+        return _metrics_dict(m)
+
     def timeline(self, ticket: int):
         """(submitted, outputs on host, entropy start, entropy end, collected), us."""
         t = (ctypes.c_double * 5)()
@@ -825,6 +930,17 @@ class Encoder:
         in bytes, 0: tight); callable between frames.  peek() stays RGB888."""
         _ck(self.L.evx_encoder_set_input_format(self.h, fmt, pitch), "set_input_format")
         self._fmt, self._pitch = fmt, pitch
+
+    def set_metrics(self, sse: bool = True, ssim: bool = True) -> None:
+        """Per-frame metrics for the frames encode() codes from now on."""
+        _ck(self.L.evx_encoder_set_metrics(self.h, (METRIC_SSE if sse else 0) | (METRIC_SSIM if ssim else 0)),
+            "evx_encoder_set_metrics")
+
+    def last_metrics(self) -> dict:
+        """Metrics of the last encoded frame (Context.frame_metrics' dict)."""
+        m = _FrameMetrics()
+        _ck(self.L.evx_encoder_last_metrics(self.h, ctypes.byref(m)), "evx_encoder_last_metrics")
+        return _metrics_dict(m)
 
     def encode(self, rgb: np.ndarray, bs: BitStream, width: int | None = None, height: int | None = None) -> None:
         """Encode one frame.  With the default input format, rgb is (height,

@@ -6,7 +6,8 @@
 //     encoder/decoder), one per frame in flight, each with its own
 //     source planes (convert output), output_cache planes (coefficients),
 //     block table, inter-search records, granules, RGB staging and pinned
-//     host buffers for the table + coefficients
+//     host buffers for the table + coefficients; with cairo_ctx_set_metrics
+//     also a plane set that keeps the frame's deblocked reconstruction
 //   sync          batch flags (zeroed per launch)
 // Frames are submitted into a batch (up to batch_max, cairo_default_batch)
 // that is launched when full or when a caller waits on one of its frames:
@@ -32,6 +33,7 @@
 #include "../../include/cairo_amd.h"
 #include "ctx_internal.h"
 #include "kernels.h"
+#include "metrics.h"
 #include "precode.h"
 
 using namespace cairo;
@@ -87,6 +89,8 @@ struct Stage {
   int ticket = -1;
   bool busy = false;      // submitted, not yet released
   bool launched = false;  // its batch has been launched
+  bool waited = false;    // its outputs were handed to a caller (cairo_ctx_wait)
+  int mflags = 0;         // cairo_ctx_set_metrics flags in force at its submit (0 for a decoded frame)
   uint32_t index = 0, type = 0, quality = 0;
 };
 
@@ -226,6 +230,15 @@ struct cairo_ctx {
   int16_t* predeblock = nullptr;  // debug: pre-deblock reconstruction of the last frame (opt-in)
   uint64_t* stamps = nullptr;     // diagnostic phase stamps (opt-in)
   uint64_t* acct = nullptr;       // diagnostic time accounting (opt-in; CAIRO_ACCT builds fill it)
+  // Kept reconstructions and per-frame metrics (cairo_ctx_set_metrics, DESIGN
+  // §4.8): a plane set per staging slot that the frame's deblock pushes its
+  // output to (FrameArgs::push), the tile partials of metrics.hip, and each
+  // slot's result in mapped pinned host memory, written by k_metrics_finish.
+  int metrics = 0;
+  int16_t* keep = nullptr;             // [stages] plane sets
+  MetricsPartial* met_part = nullptr;  // [stages][3][metrics_tiles(w, h)]
+  cairo_frame_metrics* met_host = nullptr;  // [stages]
+  cairo_frame_metrics* met_dev = nullptr;   // its device-visible address
   // Thread safety (the frame pipeline of pipeline.cpp calls in from its
   // completion and entropy threads): every public entry point holds mu;
   // HIP event waits on a frame's outputs run outside it.  launched_cv is
@@ -439,12 +452,13 @@ void free_ctx(cairo_ctx* c) {
   if (c->feed_host) (void)hipHostFree(c->feed_host);
   if (c->fs) (void)hipStreamDestroy(c->fs);
   if (c->trace_host) (void)hipHostFree(c->trace_host);
+  if (c->met_host) (void)hipHostFree(c->met_host);
   leave_group(c);
   for (int16_t* q : c->coef)
     if (q) (void)hipFree(q);
   for (void* p : {(void*)c->fdesc, (void*)c->order, (void*)c->src, (void*)c->table, (void*)c->idesc, (void*)c->progress, (void*)c->feed_dev, (void*)c->feed_hdr, (void*)c->feed_scratch,
                   (void*)c->gran, (void*)c->rgb, (void*)c->ring_buf, (void*)c->sync, (void*)c->sticky,
-                  (void*)c->predeblock, (void*)c->stamps, (void*)c->acct})
+                  (void*)c->predeblock, (void*)c->stamps, (void*)c->acct, (void*)c->keep, (void*)c->met_part})
     (void)hipFree(p);
   if (c->us) (void)hipStreamSynchronize(c->us);
   if (c->up_last) (void)hipEventDestroy(c->up_last);
@@ -692,6 +706,26 @@ int flush(cairo_ctx* c) {
   const int last = c->pend[e.nframes - 1].slot;
   const uint32_t last_epoch = c->pend[e.nframes - 1].epoch;
   if (c->predeblock) CK(launch_unpack_granules(e, e.nframes - 1, planes_at(c->predeblock, c), st));
+  // Per-frame metrics: one launch for the batch, after k_batch_wait on the
+  // launch's stream (every push store of the batch has been drained by then,
+  // DESIGN §4.8) and before the precode, so that every path to a frame's
+  // d2h_done below already follows it.
+  if (c->metrics & (CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM)) {
+    MetricsArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.w = e.w, ma.h = e.h, ma.pitch = e.wa;
+    ma.flags = c->metrics;
+    for (int i = 0; i < e.nframes; i++) {
+      if (c->pend[i].decode) continue;
+      const int slot = c->pend[i].slot;
+      ma.a[ma.nframes] = fh[i].in;
+      ma.b[ma.nframes] = slot_planes(c->keep, c, slot);
+      ma.slot[ma.nframes++] = slot;
+    }
+    ma.part = c->met_part;
+    ma.out = c->met_dev;
+    CK(launch_metrics(ma, st));
+  }
   hipStream_t ost = st;  // the stream the launch's outputs complete on
   if (c->outputs & CAIRO_OUT_FEED) {  // the entropy precode, straight into mapped host memory
     FeedArgs fa;
@@ -832,6 +866,10 @@ void frame_links(cairo_ctx* c, FrameDesc& f, int t) {
   for (int k = 0; k < kMaxRing; k++)
     f.recon[k] = slot_planes(c->ring_buf, c, k < R ? (int)(((uint32_t)f.index + R - k) % R) : 0);
   f.npush = 0;
+  if (c->metrics && !f.decode) {  // the deblock stores the frame into its slot's keep as well
+    f.npush = 1;
+    f.push[0] = slot_planes(c->keep, c, f.slot);
+  }
   f.stale = f.recon[0];
   const int ps = (t + c->stages - 1) % c->stages;
   f.coef = coef_planes(c, f.slot);
@@ -1189,6 +1227,8 @@ static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int
   c->npend++;
   s.busy = true;
   s.launched = false;
+  s.waited = false;
+  s.mflags = c->metrics;
   s.ticket = t;
   s.index = index;
   s.type = type;
@@ -1308,6 +1348,10 @@ static int frame_result(cairo_ctx* c, Stage& s, cairo_frame_result* out, bool po
   out->index = s.index;
   out->type = s.type;
   out->quality = s.quality;
+  if (s.mflags) {  // (set at its submit, under mu, before this frame could be waited on)
+    std::lock_guard<std::mutex> lk(c->mu);
+    s.waited = true;  // cairo_ctx_frame_metrics / fetch_recon may be used now
+  }
   return kSuccess;
 }
 
@@ -1324,6 +1368,30 @@ int cairo_ctx_wait(cairo_ctx* c, int ticket, cairo_frame_result* out) {
     }
   }
   return frame_result(c, s, out);
+}
+
+// A frame staged tight on the device (frame_bytes long, rows of `tight` bytes;
+// fmt < 0: RGB888) to the caller's host buffer: one copy when that is tight
+// too, else row by row per plane, so the caller's pitch padding keeps its
+// bytes.  Asynchronous on st.
+static int download_frame(const cairo_ctx* c, uint8_t* dst, const uint8_t* staged, int fmt, uint32_t pitch,
+                          uint32_t tight, uint64_t frame_bytes, hipStream_t st) {
+  if (fmt < 0 || !pitch || pitch == tight) {
+    CK(hipMemcpyAsync(dst, staged, (size_t)frame_bytes, hipMemcpyDeviceToHost, st));
+    return kSuccess;
+  }
+  const size_t w = c->w, h = c->h;
+  CK(hipMemcpy2DAsync(dst, pitch, staged, tight, tight, h, hipMemcpyDeviceToHost, st));
+  uint8_t* dc = dst + (size_t)pitch * h;
+  const uint8_t* sc = staged + w * h;
+  if (fmt == CAIRO_FMT_I420) {
+    const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
+    CK(hipMemcpy2DAsync(dc, cp, sc, cw, cw, ch, hipMemcpyDeviceToHost, st));
+    CK(hipMemcpy2DAsync(dc + cp * ch, cp, sc + cw * ch, cw, cw, ch, hipMemcpyDeviceToHost, st));
+  } else if (fmt == CAIRO_FMT_NV12) {
+    CK(hipMemcpy2DAsync(dc, pitch, sc, w, w, h / 2, hipMemcpyDeviceToHost, st));
+  }
+  return kSuccess;
 }
 
 // cairo_ctx_decode_frame (fmt < 0: RGB888 through k_yuv_to_rgb, as ever) and
@@ -1361,6 +1429,8 @@ static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef,
   c->npend = 1;
   s.busy = true;
   s.launched = false;
+  s.waited = false;
+  s.mflags = 0;
   s.ticket = t;
   s.index = index;
   s.type = 1;
@@ -1380,23 +1450,7 @@ static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef,
     if (r == kSuccess)
       r = fail(hipMemcpyAsync(s.err, c->sticky, TimeoutInfo::kWords * sizeof(int32_t), hipMemcpyDeviceToHost, st),
                "hipMemcpyAsync");
-    if (r == kSuccess && (fmt < 0 || !pitch || pitch == tight)) {
-      r = fail(hipMemcpyAsync(rgb, drgb, (size_t)frame_bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    } else if (r == kSuccess) {  // row by row: the caller's pitch padding keeps its bytes
-      const size_t w = c->w, h = c->h;
-      r = fail(hipMemcpy2DAsync(rgb, pitch, drgb, tight, tight, h, hipMemcpyDeviceToHost, st), "hipMemcpy2DAsync");
-      uint8_t* dc = rgb + (size_t)pitch * h;
-      const uint8_t* sc = drgb + w * h;
-      if (r == kSuccess && fmt == CAIRO_FMT_I420) {
-        const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
-        r = fail(hipMemcpy2DAsync(dc, cp, sc, cw, cw, ch, hipMemcpyDeviceToHost, st), "hipMemcpy2DAsync");
-        if (r == kSuccess)
-          r = fail(hipMemcpy2DAsync(dc + cp * ch, cp, sc + cw * ch, cw, cw, ch, hipMemcpyDeviceToHost, st),
-                   "hipMemcpy2DAsync");
-      } else if (r == kSuccess && fmt == CAIRO_FMT_NV12) {
-        r = fail(hipMemcpy2DAsync(dc, pitch, sc, w, w, h / 2, hipMemcpyDeviceToHost, st), "hipMemcpy2DAsync");
-      }
-    }
+    if (r == kSuccess) r = download_frame(c, rgb, drgb, fmt, pitch, tight, frame_bytes, st);
     if (r == kSuccess) r = fail(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (r == kSuccess && s.err[TimeoutInfo::kKind]) {
       report_timeout_host(c, s.err, index, st);  // (mu held: the launch stream, idle now)
@@ -1478,6 +1532,103 @@ int cairo_ctx_fetch_coef(cairo_ctx* c, int ticket, cairo_frame_result* out) {
   out->coef_y = s.coef;
   out->coef_u = s.coef + (size_t)c->wa * c->ha;
   out->coef_v = out->coef_u + (size_t)(c->wa / 2) * (c->ha / 2);
+  return kSuccess;
+}
+
+int cairo_ctx_set_metrics(cairo_ctx* c, int flags) {
+  constexpr int kAll = CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM | CAIRO_KEEP_RECON;
+  if (!c || flags < 0 || (flags & ~kAll)) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->gsize > 1) return kInvalidArg;  // a mirrored group may use every push target itself
+  CK(hipSetDevice(c->device));
+  int r = sync_all(c);  // frames in flight keep the setting they were submitted with
+  if (r) return r;
+  for (const Stage& s : c->st)
+    if (s.busy) return kInvalidResource;
+  if (flags) flags |= CAIRO_KEEP_RECON;
+  if (flags && !c->keep) {  // all or nothing
+    const size_t S = (size_t)c->stages;
+    int16_t* keep = nullptr;
+    MetricsPartial* part = nullptr;
+    cairo_frame_metrics* host = nullptr;
+    hipError_t e = hipMalloc(&keep, c->plane_elems * 2 * S);
+    if (e == hipSuccess) e = hipMalloc(&part, sizeof(MetricsPartial) * 3 * metrics_tiles((int)c->w, (int)c->h) * S);
+    if (e == hipSuccess) e = hipHostMalloc(&host, sizeof(cairo_frame_metrics) * S, hipHostMallocMapped);
+    cairo_frame_metrics* dev = nullptr;
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dev, host, 0);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(keep);
+      (void)hipFree(part);
+      if (host) (void)hipHostFree(host);
+      fprintf(stderr, "[cairo_amd] set_metrics: %s (%zu bytes of kept reconstructions)\n", hipGetErrorString(e),
+              c->plane_elems * 2 * S);
+      return e == hipErrorOutOfMemory ? kOutOfMemory : kHardwareFail;
+    }
+    memset(host, 0, sizeof(cairo_frame_metrics) * S);
+    c->keep = keep, c->met_part = part, c->met_host = host, c->met_dev = dev;
+  } else if (!flags && c->keep) {  // nothing is in flight: back to the path without a keep
+    (void)hipFree(c->keep);
+    (void)hipFree(c->met_part);
+    (void)hipHostFree(c->met_host);
+    c->keep = nullptr, c->met_part = nullptr, c->met_host = nullptr, c->met_dev = nullptr;
+  }
+  c->metrics = flags;
+  return kSuccess;
+}
+
+// The stage of a waited, unreleased, encoded frame that was submitted with a
+// keep (mu held); nullptr otherwise.
+static Stage* kept_stage(cairo_ctx* c, int ticket) {
+  if (ticket < 0) return nullptr;
+  Stage& s = c->st[ticket % c->stages];
+  if (s.ticket != ticket || !s.busy || !s.waited || !s.mflags || !c->keep) return nullptr;
+  return &s;
+}
+
+int cairo_ctx_frame_metrics(cairo_ctx* c, int ticket, cairo_frame_metrics* out) {
+  if (!c || !out) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const Stage* s = kept_stage(c, ticket);
+  if (!s || !(s->mflags & (CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM))) return kInvalidArg;
+  // written by k_metrics_finish before the frame's d2h_done, which its wait saw
+  memcpy(out, (const void*)(c->met_host + ticket % c->stages), sizeof(*out));
+  return kSuccess;
+}
+
+int cairo_ctx_fetch_recon_planes(cairo_ctx* c, int ticket, int16_t* y, int16_t* u, int16_t* v) {
+  if (!c) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!kept_stage(c, ticket)) return kInvalidArg;
+  CK(hipSetDevice(c->device));
+  if (!c->fs) CK(hipStreamCreateWithFlags(&c->fs, hipStreamNonBlocking));
+  const PlaneSet p = slot_planes(c->keep, c, ticket % c->stages);
+  const size_t ly = (size_t)c->wa * c->ha, lc = ly / 4;
+  if (y) CK(hipMemcpyAsync(y, p.y, ly * 2, hipMemcpyDeviceToHost, c->fs));
+  if (u) CK(hipMemcpyAsync(u, p.u, lc * 2, hipMemcpyDeviceToHost, c->fs));
+  if (v) CK(hipMemcpyAsync(v, p.v, lc * 2, hipMemcpyDeviceToHost, c->fs));
+  CK(hipStreamSynchronize(c->fs));
+  return kSuccess;
+}
+
+int cairo_ctx_fetch_recon(cairo_ctx* c, int ticket, int fmt, uint32_t pitch, uint8_t* out) {
+  if (!c || !out) return kInvalidArg;
+  uint64_t frame_bytes = 0;
+  uint32_t tight = 0;
+  if (cairo_frame_layout(fmt, c->w, c->h, pitch, nullptr, &tight) != kSuccess) return kInvalidArg;
+  (void)cairo_frame_layout(fmt, c->w, c->h, 0, &frame_bytes, nullptr);  // as staged: tight
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!kept_stage(c, ticket)) return kInvalidArg;
+  CK(hipSetDevice(c->device));
+  if (!c->fs) CK(hipStreamCreateWithFlags(&c->fs, hipStreamNonBlocking));
+  // staged in the slot's frame buffer: its own frame was converted before the
+  // wait, and the next upload into it follows the ticket's release
+  const int slot = ticket % c->stages;
+  uint8_t* staged = c->rgb + (size_t)slot * c->w * c->h * 3;
+  CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, fmt, tight, staged, c->fs));
+  const int r = download_frame(c, out, staged, fmt, pitch, tight, frame_bytes, c->fs);
+  if (r) return r;
+  CK(hipStreamSynchronize(c->fs));
   return kSuccess;
 }
 
@@ -1585,6 +1736,7 @@ int cairo_ctx_join_group(cairo_ctx* c, int size, int rank, const cairo_peer* pee
   if (!c || !peers || size < 1 || size > kMaxGroup || rank < 0 || rank >= size) return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
   if (!c->fresh || c->npend || c->gsize > 1) return kInvalidResource;
+  if (c->metrics) return kInvalidArg;  // a member's deblock pushes to its mirrors, not to a keep
   CK(hipSetDevice(c->device));
   if (size == 1) return kSuccess;
   const pid_t me = getpid();

@@ -49,6 +49,7 @@ class gpu_encoder : public evx1_encoder {
     ctx_ = nullptr;
     free(last_table_);
     last_table_ = nullptr;
+    has_metrics_ = false;
     initialized_ = false;
     return EVX_SUCCESS;
   }
@@ -108,6 +109,7 @@ class gpu_encoder : public evx1_encoder {
               res.feed_status == CAIRO_FEED_VALID ? "gpu" : "host");
     }
     memcpy(last_table_, res.block_table, (size_t)res.wmb * res.hmb * 16);
+    has_metrics_ = metrics_ && cairo_ctx_frame_metrics(ctx_, ticket, &last_metrics_) == 0;
     cairo_ctx_release(ctx_, ticket);
     if (r) return EVX_ERROR_EXECUTION_FAILURE;
     output->advance_write_index((uint32)(pos - output->query_write_index()));
@@ -203,6 +205,22 @@ class gpu_encoder : public evx1_encoder {
     pitch_ = pitch;
     return EVX_SUCCESS;
   }
+  // CAIRO_METRIC_* for the frames coded from now on (between frames too; the
+  // synchronous encode() leaves no frame in flight), and the last frame's.
+  evx_status set_metrics(int flags) {
+    if (flags < 0 || (flags & ~(CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM | CAIRO_KEEP_RECON))) return EVX_ERROR_INVALIDARG;
+    if (initialized_) {
+      const int r = cairo_ctx_set_metrics(ctx_, flags);
+      if (r) return (evx_status)r;
+    }
+    metrics_ = flags;
+    return EVX_SUCCESS;
+  }
+  evx_status last_metrics(cairo_frame_metrics *out) const {
+    if (!out || !has_metrics_) return EVX_ERROR_INVALIDARG;
+    *out = last_metrics_;
+    return EVX_SUCCESS;
+  }
 
  private:
   void reset_frame() {  // clear_frame, common.cpp:50-65
@@ -217,6 +235,7 @@ class gpu_encoder : public evx1_encoder {
     if (cairo_ctx_create_ex(width, height, ring_, device_, 2, &ctx_)) return EVX_ERROR_HARDWAREFAIL;
     // the GPU precodes the entropy feed; only the arithmetic coder runs here
     if (cairo_ctx_set_outputs(ctx_, CAIRO_OUT_FEED)) return EVX_ERROR_HARDWAREFAIL;
+    if (metrics_ && cairo_ctx_set_metrics(ctx_, metrics_)) return EVX_ERROR_HARDWAREFAIL;
     const size_t mbs = (size_t)((width + 15) / 16) * ((height + 15) / 16);
     last_table_ = (uint8 *)calloc(mbs, 16);
     if (!last_table_) return EVX_ERROR_OUTOFMEMORY;
@@ -236,6 +255,9 @@ class gpu_encoder : public evx1_encoder {
   uint32 pitch_ = 0;
   cairo_ctx *ctx_ = nullptr;
   uint8 *last_table_ = nullptr;
+  int metrics_ = 0;  // set_metrics
+  bool has_metrics_ = false;
+  cairo_frame_metrics last_metrics_ = {};
 };
 
 evx_status create_encoder(evx1_encoder **output) {
@@ -278,6 +300,13 @@ int evx_encoder_set_device(void *enc, int device) {
 }
 int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch) {
   return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_format(fmt, pitch);
+}
+
+int evx_encoder_set_metrics(void *enc, int flags) {
+  return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_metrics(flags);
+}
+int evx_encoder_last_metrics(void *enc, cairo_frame_metrics *out) {
+  return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->last_metrics(out);
 }
 
 // band4 generator: deterministic synthetic content.

@@ -58,6 +58,8 @@ struct Frame {
   int status = kSuccess;
   std::vector<uint8_t> bits;  // payload, LSB-first from bit 0
   uint64_t nbits = 0;
+  bool has_metrics = false;  // cairo_ctx_set_metrics was on for the frame
+  cairo_frame_metrics metrics = {};
 };
 
 struct Job {
@@ -111,9 +113,15 @@ struct cairo_stream {
         finish(t, r, 0);
         continue;
       }
+      // the frame's metrics, while its ticket is unreleased (none: metrics off)
+      cairo_frame_metrics fm;
+      const bool has = cairo_ctx_frame_metrics(ctx, t, &fm) == kSuccess;
       {
         std::lock_guard<std::mutex> lk(m);
-        at(t).t[kTOutputs] = now_us();
+        Frame& f = at(t);
+        f.t[kTOutputs] = now_us();
+        f.has_metrics = has;
+        if (has) f.metrics = fm;
         jobs.push_back(j);
       }
       cv.notify_all();
@@ -258,6 +266,7 @@ static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device,
     f.state = Frame::kSubmitted;
     f.status = kSuccess;
     f.nbits = 0;
+    f.has_metrics = false;
     s->todo.push_back(tk);
   }
   s->cv.notify_all();
@@ -339,6 +348,15 @@ int cairo_stream_timeline(cairo_stream* s, int ticket, double* t) {
   const Frame& f = s->at(ticket);
   if (f.ticket != ticket) return kInvalidResource;
   for (int k = 0; k < kTimes; k++) t[k] = f.t[k];
+  return kSuccess;
+}
+
+int cairo_stream_frame_metrics(cairo_stream* s, int ticket, cairo_frame_metrics* out) {
+  if (!s || !out || ticket < 0) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(s->m);
+  const Frame& f = s->at(ticket);
+  if (f.ticket != ticket || f.state == Frame::kSubmitted || !f.has_metrics) return kInvalidArg;
+  *out = f.metrics;
   return kSuccess;
 }
 

@@ -41,7 +41,12 @@ extern "C" {
  *   3  round 5: cairo_ctx_read_inter refuses stale (untagged) records
  *   4  pixel formats: cairo_frame_layout, cairo_ctx_submit_fmt,
  *      cairo_ctx_decode_frame_fmt, cairo_stream_submit_fmt, cairo_kat_convert,
- *      evx_encoder_set_input_format, evx_decoder_set_output_format */
+ *      evx_encoder_set_input_format, evx_decoder_set_output_format
+ *   4  (unchanged) per-frame metrics and kept reconstructions add entry points
+ *      only: cairo_ctx_set_metrics, cairo_ctx_frame_metrics,
+ *      cairo_ctx_fetch_recon[_planes], cairo_stream_frame_metrics,
+ *      cairo_kat_metrics, evx_encoder_set_metrics / _last_metrics.  Nothing
+ *      existing changes, so the version stays: detect them by their symbols. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -305,6 +310,80 @@ CAIRO_API int cairo_ctx_set_helpers(cairo_ctx *ctx, int helpers);
 /* Upper bound of cairo_ctx_set_workgroups on this device. */
 CAIRO_API int cairo_ctx_max_workgroups(const cairo_ctx *ctx);
 
+/* ---- per-frame distortion and kept reconstructions --------
+ * A frame's deblocked reconstruction lives in ring slot index % R and is
+ * overwritten R frames later, inside the same launch.  With any of the flags
+ * below the deblock also stores it into a plane set of the frame's staging
+ * slot (the "keep"), which stays valid until the ticket is released; the
+ * metric flags run a reduction kernel over it after the launch. */
+#define CAIRO_METRIC_SSE 1  /* exact sum of squared errors per plane          */
+#define CAIRO_METRIC_SSIM 2 /* sum of SSIM window values per plane            */
+#define CAIRO_KEEP_RECON 4  /* keep the reconstruction (implied by a metric)  */
+/* Both sides are compared as the 8-bit samples the I420 output defines,
+ * Y8 = clamp(Y - 16, 0, 255), U8 = clamp(U, 0, 255), V8 = clamp(V, 0, 255),
+ * over the nominal picture: width x height luma, (width/2) x (height/2)
+ * chroma (index 0 Y, 1 U, 2 V); the padding up to 16 is excluded.  a is the
+ * source (what an I420 submit carried, or the converted RGB), b the
+ * reconstruction (what the decoder shows as I420).
+ *   sse[p]      sum of (a - b)^2, exact.  PSNR = 10 log10(255^2 * samples[p] /
+ *               sse[p]), infinite at sse 0; "all planes" uses the summed sse
+ *               over the summed samples.
+ *   SSIM        the plane is cut into 4x4 blocks from its origin, bw =
+ *               floor(pw/4) by bh = floor(ph/4); leftover columns and rows are
+ *               ignored.  A window is 2x2 blocks (8x8 samples) at block stride
+ *               1: (bw-1)*(bh-1) windows, none if bw < 2 or bh < 2.  Over a
+ *               window's 64 samples, in integers: s1 = sum a, s2 = sum b,
+ *               ss = sum (a^2 + b^2), s12 = sum a*b;
+ *                 vars  = 64*ss - s1^2 - s2^2,  covar = 64*s12 - s1*s2,
+ *                 c1 = 416, c2 = 235963   ((0.01*255)^2*64, (0.03*255)^2*64*63)
+ *                 num = (2*s1*s2 + c1) * (2*covar + c2)
+ *                 den = (s1^2 + s2^2 + c1) * (vars + c2)        (exact in int64)
+ *               and the window's value is (double)num / (double)den.
+ *   ssim_sum[p] the sum of the plane's window values (a fixed reduction order:
+ *               the same input gives the same bits), ssim_windows[p] their
+ *               count; SSIM = ssim_sum / ssim_windows.
+ * Fields of a metric that was not asked for are 0. */
+typedef struct cairo_frame_metrics {
+  uint32_t flags;          /* the CAIRO_METRIC_* computed for this frame */
+  uint32_t width, height;  /* nominal frame size */
+  uint32_t reserved;
+  uint64_t sse[3];
+  double ssim_sum[3];
+  uint64_t ssim_windows[3];
+  uint64_t samples[3];
+} cairo_frame_metrics;
+/* sizeof(cairo_frame_metrics), for bindings. */
+CAIRO_API int cairo_frame_metrics_size(void);
+/* Choose the flags for frames submitted from now on; no frame may be in
+ * flight (EVX_ERROR_INVALID_RESOURCE).  The first enabling call allocates
+ * `stages` plane sets (3 * Wa * Ha bytes each: 2.4 GB for a 4K context with 96
+ * stages; EVX_ERROR_OUTOFMEMORY leaves the context as it was), flags 0 frees
+ * them; with flags 0 a launch is what it is without this call.  Survives
+ * cairo_ctx_reset.  EVX_ERROR_INVALID_ARGS for unknown bits and for a member
+ * of a group (whose deblock already pushes to its mirrors); a context with
+ * metrics on cannot join a group. */
+CAIRO_API int cairo_ctx_set_metrics(cairo_ctx *ctx, int flags);
+/* The metrics of a waited, unreleased frame.  EVX_ERROR_INVALID_ARGS when no
+ * metric was on for it, for a decoded frame, and for a ticket that is not
+ * waited or already released. */
+CAIRO_API int cairo_ctx_frame_metrics(cairo_ctx *ctx, int ticket, cairo_frame_metrics *out);
+/* The kept reconstruction of a waited, unreleased frame as aligned int16
+ * planes, in the layout of cairo_ctx_read_planes (Wa x Ha, Wa/2 x Ha/2); any
+ * of y, u, v may be NULL.  Refused like cairo_ctx_frame_metrics. */
+CAIRO_API int cairo_ctx_fetch_recon_planes(cairo_ctx *ctx, int ticket, int16_t *y, int16_t *u, int16_t *v);
+/* The same frame in any CAIRO_FMT_* with row pitch `pitch` (0: tight) into
+ * host memory out (cairo_frame_layout bytes; the pitch padding keeps its
+ * bytes): what cairo_ctx_decode_frame_fmt writes for this frame. */
+CAIRO_API int cairo_ctx_fetch_recon(cairo_ctx *ctx, int ticket, int fmt, uint32_t pitch, uint8_t *out);
+/* Known-answer check of the metrics kernels on host buffers, without a
+ * context or the engine: planes a and b of w x h (luma; chroma (w/2) x (h/2))
+ * with pitch_elems elements per luma row and pitch_elems / 2 per chroma row
+ * (pitch_elems even, >= w), both metrics. */
+CAIRO_API int cairo_kat_metrics(uint32_t w, uint32_t h, uint32_t pitch_elems, const int16_t *a_y,
+                                const int16_t *a_u, const int16_t *a_v, const int16_t *b_y,
+                                const int16_t *b_u, const int16_t *b_v, cairo_frame_metrics *out,
+                                int device);
+
 /* Known-answer check of the device transform chain: count macroblocks of 384
  * int16 (block-major: Y TL,TR,BL,BR, U, V; 64 each).  qtype[2m] = block type,
  * qtype[2m+1] = frame quality.  Host buffers in and out. */
@@ -385,6 +464,11 @@ CAIRO_API int cairo_stream_payload_bits(cairo_stream *s, int ticket, uint64_t *n
  * submitted): t[5] = submitted, outputs on the host, entropy start, entropy
  * end, collected; microseconds of a monotonic clock. */
 CAIRO_API int cairo_stream_timeline(cairo_stream *s, int ticket, double *t);
+/* The metrics of a frame of a context with cairo_ctx_set_metrics on (set
+ * before the stream is created): copied when the pipeline picks up the
+ * frame's outputs, valid for a collected frame until ticket + 2*stages is
+ * submitted.  EVX_ERROR_INVALID_ARGS when the frame has none. */
+CAIRO_API int cairo_stream_frame_metrics(cairo_stream *s, int ticket, cairo_frame_metrics *out);
 /* Finish all submitted frames and stop the threads. */
 CAIRO_API int cairo_stream_destroy(cairo_stream *s);
 /* Append n bits of src at bit *pos of dst (cap_bits), bit_stream semantics. */
@@ -408,6 +492,11 @@ CAIRO_API int evx_encoder_set_device(void *enc, int device);  /* before first en
 /* The layout encode() reads its image in from now on (CAIRO_FMT_*, row pitch
  * in bytes, 0: tight); callable between frames.  peek() keeps writing RGB888. */
 CAIRO_API int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch);
+/* CAIRO_METRIC_* for the frames encode() codes from now on (callable between
+ * frames), and the metrics of the last encoded frame (EVX_ERROR_INVALID_ARGS
+ * when it has none). */
+CAIRO_API int evx_encoder_set_metrics(void *enc, int flags);
+CAIRO_API int evx_encoder_last_metrics(void *enc, cairo_frame_metrics *out);
 
 /* ---- drop-in decoder, C view of evx1_decoder (evx1.h:97-112) ------------
  * decode() reads [header +] one frame record from bs (its read index onward),

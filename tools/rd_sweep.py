@@ -8,6 +8,8 @@ Per quality q, on the band4 content (seed 1234), ring R = 4:
     entropy), plus the 10-byte frame descriptor the encoder writes per frame;
   * distortion: PSNR (peak 255) of the last frame's deblocked reconstruction
     against its converted source, luma and chroma separately.
+  * with --frame-metrics, the mean PSNR and SSIM over every timed frame
+    (cairo_ctx_set_metrics: the GPU's per-frame figures), as mean_* fields.
   * parity: the canonical FNV-1a-64 (tail bits and header byte 7 masked) of
     every frame's stream record that the oracle's golden stream of this quality
     covers (tests/golden/stream_4k_q<q>_r4.json, made off-box by
@@ -60,6 +62,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "rd_sweep.json"))
     ap.add_argument("--check", type=int, default=8,
                     help="frames per quality also pinned by SHA-256 (SURVEY §8(d) Config 5: >= 8)")
+    ap.add_argument("--frame-metrics", action="store_true",
+                    help="add the mean per-frame PSNR / SSIM of the timed frames (cairo_ctx_set_metrics, "
+                         "DESIGN §4.8) as new fields; the other fields are as without it")
     a = ap.parse_args()
     import torch
 
@@ -93,6 +98,8 @@ def main():
         ctx.close()
         # rate and distortion (frame pipeline: entropy on host threads)
         ctx = cairo_amd.Context(w, h, ring)
+        if a.frame_metrics:
+            ctx.set_metrics()
         st = cairo_amd.Stream(ctx, threads=14)
         tks = []
         bits = []
@@ -100,9 +107,12 @@ def main():
         gold = bench.golden_stream(a.config, "band4", q, ring)
         ncheck = min(n, gold["frames"]) if gold else 0
         fnv = []
+        per_frame = []
 
         def take(tk):
             data, nb = st.collect(tk)
+            if a.frame_metrics:
+                per_frame.append(st.frame_metrics(tk))
             t = len(bits)
             bits.append(nb)
             if t < max(a.check, ncheck):
@@ -133,6 +143,11 @@ def main():
                "psnr_u": round(psnr(src[1][:hh // 2, :ww // 2], rec[1][:hh // 2, :ww // 2]), 2),
                "psnr_v": round(psnr(src[2][:hh // 2, :ww // 2], rec[2][:hh // 2, :ww // 2]), 2),
                "pinned_frames": pins}
+        if a.frame_metrics:  # every timed frame, not only the last
+            for k in ("psnr_y", "psnr_u", "psnr_v", "psnr_all"):
+                row["mean_" + k] = round(float(np.mean([m[k] for m in per_frame[warm:]])), 2)
+            for k in ("ssim_y", "ssim_u", "ssim_v"):
+                row["mean_" + k] = round(float(np.mean([m[k] for m in per_frame[warm:]])), 5)
         mism = [t for t in range(ncheck) if fnv[t] != gold["frame_fnv1a64"][t]]
         row["golden"] = {"path": gold["path"] if gold else None, "frames_checked": ncheck,
                          "mismatches": len(mism), "mismatched_frames": mism, "frame_fnv1a64": fnv}
