@@ -409,7 +409,9 @@ class Context:
                    "coder_vm0", "coder_records", "coder_prebarrier", "coder_store_tail",
                    "search_eval", "search_barrier", "search_select", "subpel_eval", "subpel_barrier",
                    "subpel_select", "db_inputs", "db_filter", "db_write",
-                   "search_passes", "search_mbs_2pass", "search_mbs_3pass", "search_mbs_4pass")
+                   "search_passes", "search_mbs_2pass", "search_mbs_3pass", "search_mbs_4pass",
+                   "coder_xform_copy", "coder_copy_mbs", "coder_xform_coded", "coder_coded_mbs",
+                   "helper_carry", "carry_bytes")
 
     def read_acct(self, reset: bool = False) -> dict:
         """Engine time accounting (set_debug(32) on a CAIRO_ACCT=1 build): 10 ns

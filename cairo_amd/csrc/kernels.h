@@ -112,7 +112,7 @@ enum TimeoutKind : int32_t {
 #ifndef CAIRO_ACCT
 #define CAIRO_ACCT 0
 #endif
-constexpr int kAcctShards = 64, kAcctWords = 44;
+constexpr int kAcctShards = 64, kAcctWords = 50;
 struct Acct {
   // row coders
   static constexpr int kCoderTasks = 0, kCoderTotal = 1, kCoderGroupWait = 2, kCoderWindow = 3, kCoderSearch = 4,
@@ -144,6 +144,14 @@ struct Acct {
   // the macroblocks, and the macroblocks whose stages 1-4 took 2, 3 and 4
   // passes (stage 0 always takes one more)
   static constexpr int kSrchPasses = 40, kSrchPasses2 = 41, kSrchPasses3 = 42, kSrchPasses4 = 43;
+  // kCoderXform by macroblock kind: time and count of the copy macroblocks
+  // (type & kCopy: the output_cache carry, when the coder does it) and of the
+  // coded ones (the transform chain)
+  static constexpr int kCoderXformCopy = 44, kCoderCopyMBs = 45, kCoderXformCoded = 46, kCoderCodedMBs = 47;
+  // the helper's output_cache carry of a group: from the first
+  // load to the last store issued (its acknowledgements are waited for
+  // behind the window's DMA), and the bytes carried
+  static constexpr int kHelperCarry = 48, kCarryBytes = 49;
 };
 
 // Frames per engine launch.

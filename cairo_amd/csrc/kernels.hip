@@ -1055,10 +1055,80 @@ __device__ __forceinline__ int inter_need_cols(FA& a, int g, int level) {
   return min(64 * g + (level == 1 ? 80 : 96), a.wa);
 }
 
+// Build switch (accounting and A/B builds): 1 keeps the output_cache carry of
+// copy macroblocks in the row coder on inter frames too, as before §4.9.
+#ifndef CAIRO_CODER_CARRY
+#define CAIRO_CODER_CARRY 0
+#endif
+
+// 16 bytes stored write-through like coef_store_pair's dwords (sc1: agent
+// scope; sc0 sc1: the system-scope form, for a view shared across devices).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) u32x4 gbl_u32x4;
+__device__ __forceinline__ void store16_through(bool sys, int16_t* p, u32x4 v) {
+  if (sys)
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+  else
+    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+}
+
+// The output_cache carry of group g of row r of an inter frame:
+// a copy macroblock keeps its previous coefficients, and every frame has its
+// own coefficient planes, so the helper copies the group's macroblocks
+// 4g .. min(4g+3, wmb-1) from coef_prev to coef before the group's records
+// exist; the coder then stores only what it codes, over the carried values.
+// 192 lanes, 16 bytes each: lanes 0..127 the 16 luma rows (128 contiguous
+// bytes per row, 8 chunks), 128..159 the 8 U rows (4 chunks: one per
+// macroblock), 160..191 the 8 V rows; columns of macroblocks >= wmb masked.
+// One load per lane, so every load of a wave is issued before its first store.
+//
+// After helper_wait(a, 1, r, min(r + 2, hmb - 1), 64g + 80 columns): the
+// previous frame's row r+2 (clamped to the last row) deblocked that far only
+// after its row r was coded through column 64g + 80 -- the deblock of a row
+// reads its own coder's info granules, which follow the macroblock's drained
+// coefficient stores, and waits for the row above's progress, so rows r+1 and
+// r are past that column too -- and the previous frame's own carry of this
+// group was acknowledged before the records its coder acquired (below).  The
+// same wait says every earlier reader of this slot's old coefficients is done
+// (they are frames <= index-1 reading at or before that column).
+//
+// Release: the group's reference-1 records are its ready flag, so no such
+// record may be stored before every wave's carry stores are acknowledged
+// (s_waitcnt vmcnt(0), then a workgroup barrier: inter_task).  The next
+// frame sees the carried values through: this acknowledged carry -> the
+// records -> the coder's acquire -> its info granule -> the deblock ->
+// the progress word -> the next frame's helper_wait.
+// Returns whether anything was stored (workgroup-uniform): not when coef and
+// coef_prev are the same planes (one staging slot).
+__device__ __forceinline__ bool carry_group(FA& a, int r, int g) {
+  if (CAIRO_CODER_CARRY) return false;
+  const PlaneSet dst = planes(a.coef), src = planes(a.coef_prev);
+  if (dst.y == src.y) return false;
+  const uint64_t t0 = acct_now();
+  const int t = threadIdx.x;
+  int pl, row, x, col;  // plane, plane row, macroblock column, first plane column of this lane's chunk
+  if (t < 128) {
+    pl = 0, row = r * kMB + (t >> 3), x = 4 * g + ((t & 7) >> 1), col = 4 * g * kMB + 8 * (t & 7);
+  } else {
+    const int k = t - 128;
+    pl = 1 + (k >> 5), row = r * (kMB / 2) + ((k & 31) >> 2), x = 4 * g + (k & 3), col = x * (kMB / 2);
+  }
+  if (t < 192 && x < a.wmb) {
+    const size_t off = (size_t)row * (pl ? a.wa >> 1 : a.wa) + col;
+    const u32x4 v = *(const gbl_u32x4*)(pick(src, pl) + off);
+    store16_through(a.sys, pick(dst, pl) + off, v);
+  }
+  acct_add(a.acct, Acct::kHelperCarry, acct_now() - t0);
+  acct_add(a.acct, Acct::kCarryBytes, 768ull * (uint64_t)min(4, a.wmb - 4 * g));
+  return true;
+}
+
 // Reference offset `off` of group g of row r: the tagged records of the
 // group's macroblocks are stored and left in flight (the coder polls them).
+// carried: carry_group stored this group's coefficients (off == 1 only); they
+// are acknowledged before the records are stored.
 __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterLds& L, DbLds& D, DbState& st,
-                                           int* flag, uint64_t* is) {
+                                           int* flag, uint64_t* is, bool carried = false) {
   FA& a = *opaque_view(&a0);
   const int wave = uni(threadIdx.x >> 6);  // scalar: the acceptance replay runs on SGPRs
   const int x = 4 * g + wave;
@@ -1113,6 +1183,8 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
     const bool full = L.full != 0;  // workgroup-uniform
     acct_add(a.acct, Acct::kSearchedTasks, 1);
     acct_window(a.acct, 0, full ? kWinL : kLvl1Rows, 0, full ? kWinLW : kLvl1Cols);
+    // (the DMA's vmcnt(0) and barrier in here are also the carry's release:
+    // every wave's carry stores, issued before its DMA, are acknowledged)
     stage_window(L.win, ref, a.wa, a.ha, ox, oy, 0, full ? kWinL : kLvl1Rows, 0, full ? kWinLW : kLvl1Cols);
     __syncthreads();
     if (is && off == 1) is[4] = __builtin_amdgcn_s_memrealtime();
@@ -1244,6 +1316,11 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
         }
       }
     }
+  } else if (carried) {
+    // no search, so no DMA wait: the carry's release on its own (every wave's
+    // carry stores acknowledged, then the barrier) before the records
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   }
   if (is && off == 1) is[10] = __builtin_amdgcn_s_memrealtime();
   if (valid && (threadIdx.x & 63) == 0) {
@@ -1780,7 +1857,8 @@ constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0) expcnt(7) lgkmcnt(15) (g
 
 // A macroblock's end waits only for its coefficient stores (which its info
 // granule releases to the deblock and, through its progress, to the next
-// frame's copy macroblocks), not for the pixel-granule and table stores
+// frame's carry of the group: carry_group), not for the pixel-granule and
+// table stores
 // issued after them: vmcnt retires in order, so wave w waits until no more
 // than the stores it issued after its last coefficient store are
 // outstanding.  Those are, in program order (compiler barriers keep it):
@@ -2486,6 +2564,11 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
           int16_t qv;
           if (!kDecode) {
             qv = (CAIRO_ATTR_SKIP & 64) ? (int16_t)cf[bi] : quant_elem(e, cf[bi], qp, intra_path);
+            // Over the value the helper carried here (inter frames): this
+            // coder acquired the group's records before any store of
+            // macroblocks 4g..4g+3 (the classification above waits for them),
+            // and the helper's carry stores were acknowledged before those
+            // records were stored, so this store is the last one written.
             coef_store_pair(*ap, e, px, py, qv);
           } else {  // the decoded coefficients (the decoder's input_cache)
             int pl, ex, ey;
@@ -2504,7 +2587,11 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       } else {  // copy: output_cache keeps this macroblock's previous coefficients
         d.q_index = 0;
         d.variance = 0;
-        if (!kDecode) {
+        // Inter frames: the row's helper carried them before it stored the
+        // group's records (carry_group), so there is nothing to load, store
+        // or drain here.  Intra frames (their helpers only carry the
+        // dependency) keep the carry below; a decode launch reads coef.
+        if (!kDecode && (!ap->inter || CAIRO_CODER_CARRY)) {  // workgroup-uniform
           int cp[2] = {0, 0};  // both loads issued before the first store (which may alias them)
           _Pragma("unroll") for (int bi = 0; bi < 2; bi++) if (bi < nblk) {
             const int e = (wave + 4 * bi) * 64 + lane;
@@ -2523,8 +2610,10 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       // pairs (lane, lane^1) of each 8x8 block as granules.  No drain before
       // them: the coefficient stores only have to be visible to whoever
       // observes the info granule below (the deblock, and through its
-      // progress the next frame's copy macroblocks), which is stored after
-      // the drain.
+      // progress the next frame's helper, which carries them: carry_group),
+      // which is stored after the drain.  A copy macroblock of an inter frame
+      // stores no coefficient; its drain below then waits for nothing it
+      // issued here (the helper's carry was acknowledged before the records).
       _Pragma("unroll") for (int bi = 0; bi < 2; bi++) if (bi < nblk) {
         const int b = wave + 4 * bi;
         const int nb = __builtin_amdgcn_mov_dpp(pv[bi], 0xB1, 0xF, 0xF, false);  // lane ^ 1
@@ -2572,6 +2661,9 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       if (CAIRO_ACCT) {
         const uint64_t tx9 = acct_now();
         acct_add(ap->acct, Acct::kCoderXform, tx7 - tx5);
+        const bool cpy = (type & kCopy) != 0;  // the same phase by macroblock kind
+        acct_add(ap->acct, cpy ? Acct::kCoderXformCopy : Acct::kCoderXformCoded, tx7 - tx5);
+        acct_add(ap->acct, cpy ? Acct::kCoderCopyMBs : Acct::kCoderCodedMBs, 1);
         acct_add(ap->acct, Acct::kCoderPublish, tx8 - tx7);
         acct_add(ap->acct, Acct::kCoderDrain, tx9 - tx8);
       }
@@ -2634,8 +2726,11 @@ __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* fla
     if (is) is[1] = __builtin_amdgcn_s_memrealtime();
     trace(tr, 3, 50);
     if (a.inter) {
+      // the group's output_cache carry, right after the wait (which covers
+      // coef_prev: carry_group); released by inter_task before the records
+      const bool carried = carry_group(a, r, g);
       const uint64_t ts = acct_now();
-      inter_task(a, r, g, 1, L.inter, L.db, st, flag, is);
+      inter_task(a, r, g, 1, L.inter, L.db, st, flag, is, carried);
       acct_add(a.acct, Acct::kHelperSearch, acct_now() - ts);
     } else if (tid == 0) {  // intra frame: carry the dependency only
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
