@@ -97,6 +97,11 @@ def lib() -> ctypes.CDLL:
         "cairo_stream_submit_fmt": (I, [P, P, I, I, U, U, U, U, ctypes.POINTER(I)]),
         "evx_encoder_set_input_format": (I, [P, I, U]),
         "evx_decoder_set_output_format": (I, [P, I, U]),
+        "cairo_source_size": (I, []),
+        "cairo_scale_check": (I, [I, U, P, U, U]),
+        "cairo_ctx_submit_scaled": (I, [P, P, I, U, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_stream_submit_scaled": (I, [P, P, I, U, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_kat_scale": (I, [I, U, P, P, U, U, P, I]),
         "cairo_frame_metrics_size": (I, []),
         "cairo_ctx_set_metrics": (I, [P, I]),
         "cairo_ctx_frame_metrics": (I, [P, I, P]),
@@ -256,6 +261,82 @@ def _host_frame_fmt(frame, fmt: int, width: int, height: int, pitch: int) -> int
     return frame.ctypes.data
 
 
+class _Source(ctypes.Structure):
+    """cairo_source (include/cairo_amd.h): the source frame of a scaled submit."""
+    _fields_ = [
+        ("width", ctypes.c_uint32),
+        ("height", ctypes.c_uint32),
+        ("crop_x", ctypes.c_uint32),
+        ("crop_y", ctypes.c_uint32),
+        ("crop_w", ctypes.c_uint32),
+        ("crop_h", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
+KAT_SCALE_GUARD = 64  # CAIRO_KAT_SCALE_GUARD
+
+
+def _source(src_size, crop) -> "_Source":
+    vals = tuple(src_size) + (tuple(crop) if crop is not None else (0, 0, 0, 0))
+    if len(vals) != 6 or not all(isinstance(x, (int, np.integer)) and 0 <= x < 2 ** 32 for x in vals):
+        raise ValueError(f"src_size is (w, h) and crop (x, y, w, h) in 0..2^32-1, got {src_size} {crop}")
+    return _Source(*(int(x) for x in vals))
+
+
+def scale_check(fmt: int, src_size, dst_w: int, dst_h: int, crop=None, pitch: int = 0) -> bool:
+    """Whether a source frame of src_size = (w, h), format fmt and row pitch
+    `pitch` (0: tight), or its region crop = (x, y, w, h), can be scaled to
+    dst_w x dst_h (cairo_scale_check): even sizes and crop values, the crop
+    inside the source, a copy or a downscale of at most 8:1 per axis, and
+    255 Lx Ly < 2^31.  No device needed."""
+    ok = all(isinstance(x, (int, np.integer)) and 0 <= x < 2 ** 32 for x in (pitch, dst_w, dst_h)) and \
+        isinstance(fmt, (int, np.integer)) and -2 ** 31 <= fmt < 2 ** 31
+    if not ok:
+        return False
+    try:
+        s = _source(src_size, crop)
+    except (ValueError, TypeError):
+        return False
+    return lib().cairo_scale_check(int(fmt), int(pitch), ctypes.byref(s), int(dst_w), int(dst_h)) == EVX_SUCCESS
+
+
+def kat_scale(frame: np.ndarray, fmt: int, src_size, dst_w: int, dst_h: int, crop=None, pitch: int = 0,
+              out: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """The scaling kernel on a host frame, without a context (cairo_kat_scale):
+    -> the tight dst_w x dst_h frame followed by KAT_SCALE_GUARD bytes the
+    kernel must leave alone (0xA5 unless `out` brings its own contents).  The
+    device copy keeps frame's address modulo 4."""
+    sw, sh = src_size
+    nb, _ = frame_layout(fmt, sw, sh, pitch)
+    db, _ = frame_layout(fmt, dst_w, dst_h)
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.nbytes != nb or \
+            not frame.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"frame must be a C-contiguous uint8 array of {nb} bytes")
+    if out is None:
+        out = np.full(db + KAT_SCALE_GUARD, 0xA5, np.uint8)
+    elif out.dtype != np.uint8 or out.nbytes != db + KAT_SCALE_GUARD or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"out must be a C-contiguous uint8 array of {db + KAT_SCALE_GUARD} bytes")
+    s = _source(src_size, crop)
+    _ck(lib().cairo_kat_scale(fmt, pitch, ctypes.byref(s), frame.ctypes.data, dst_w, dst_h, _ptr(out), device),
+        "cairo_kat_scale")
+    return out
+
+
+def _scaled_source_ptr(frame, on_device: bool, fmt: int, src_size, pitch: int) -> int:
+    """Address of the source of a scaled submit.  Only device sources are
+    scaled; a host array is still checked and handed over, so that the refusal
+    is the library's (EVX_ERROR_INVALID_ARGS)."""
+    if on_device:
+        return frame
+    nb, _ = frame_layout(fmt, src_size[0], src_size[1], pitch)
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.nbytes != nb or \
+            not frame.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"a format {fmt} source of {src_size[0]}x{src_size[1]}, pitch {pitch} is a C-contiguous uint8 "
+                         f"array of {nb} bytes")
+    return frame.ctypes.data
+
+
 def make_band4(w: int, h: int, t: int, seed: int = 1234) -> np.ndarray:
     """band4 synthetic RGB888 frame, shape (h, w, 3)."""
     out = np.empty((h, w, 3), np.uint8)
@@ -376,10 +457,22 @@ class Context:
         return int(self.L.cairo_ctx_stages(self.h))
 
     def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
-               fmt: int = FMT_RGB24, pitch: int = 0) -> int:
+               fmt: int = FMT_RGB24, pitch: int = 0, src_size=None, crop=None) -> int:
         """fmt / pitch: the frame's layout (FMT_*, row pitch in bytes, 0:
-        tight); the defaults are today's tight RGB888 through cairo_ctx_submit."""
+        tight); the defaults are today's tight RGB888 through cairo_ctx_submit.
+        src_size = (w, h): the frame is a larger device frame of that size (and
+        pitch), scaled to the context's size on the GPU before it is encoded
+        (cairo_ctx_submit_scaled, see scale_check); crop = (x, y, w, h) scales a
+        region of it."""
         t = ctypes.c_int()
+        if src_size is not None or crop is not None:
+            if src_size is None:
+                raise ValueError("crop needs src_size")
+            s = _source(src_size, crop)
+            ptr = _scaled_source_ptr(rgb, on_device, fmt, src_size, pitch)
+            _ck(self.L.cairo_ctx_submit_scaled(self.h, ptr, fmt, pitch, ctypes.byref(s), index, int(inter), quality,
+                                               ctypes.byref(t)), "cairo_ctx_submit_scaled")
+            return t.value
         ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, self.width, self.height, pitch)
         if fmt == FMT_RGB24 and not pitch:
             _ck(
@@ -508,8 +601,8 @@ class Context:
         _ck(self.L.cairo_ctx_release(self.h, ticket), "cairo_ctx_release")
 
     def encode_frame(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
-                     fmt: int = FMT_RGB24, pitch: int = 0) -> FrameOutputs:
-        t = self.submit(rgb, index, inter, quality, on_device, fmt=fmt, pitch=pitch)
+                     fmt: int = FMT_RGB24, pitch: int = 0, src_size=None, crop=None) -> FrameOutputs:
+        t = self.submit(rgb, index, inter, quality, on_device, fmt=fmt, pitch=pitch, src_size=src_size, crop=crop)
         try:
             return self.wait(t, copy=True)
         finally:
@@ -679,9 +772,10 @@ class Group:
         self.tickets = {}
 
     def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
-               fmt: int = FMT_RGB24, pitch: int = 0) -> None:
+               fmt: int = FMT_RGB24, pitch: int = 0, src_size=None, crop=None) -> None:
         m = self.members[index % self.size]
-        self.tickets[index] = m.submit(rgb, index, inter, quality, on_device, fmt=fmt, pitch=pitch)
+        self.tickets[index] = m.submit(rgb, index, inter, quality, on_device, fmt=fmt, pitch=pitch,
+                                       src_size=src_size, crop=crop)
 
     def wait(self, index: int, copy: bool = True) -> FrameOutputs:
         """Outputs of frame `index`; launches every member's pending frames first
@@ -807,8 +901,17 @@ class Stream:
         self._keep = {}
 
     def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
-               fmt: int = FMT_RGB24, pitch: int = 0) -> int:
+               fmt: int = FMT_RGB24, pitch: int = 0, src_size=None, crop=None) -> int:
+        """src_size / crop: a scaled submit, as Context.submit."""
         t = ctypes.c_int()
+        if src_size is not None or crop is not None:
+            if src_size is None:
+                raise ValueError("crop needs src_size")
+            s = _source(src_size, crop)
+            ptr = _scaled_source_ptr(rgb, on_device, fmt, src_size, pitch)
+            _ck(self.L.cairo_stream_submit_scaled(self.h, ptr, fmt, pitch, ctypes.byref(s), index, int(inter), quality,
+                                                  ctypes.byref(t)), "cairo_stream_submit_scaled")
+            return t.value
         ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, self.ctx.width, self.ctx.height, pitch)
         if fmt == FMT_RGB24 and not pitch:
             _ck(self.L.cairo_stream_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),

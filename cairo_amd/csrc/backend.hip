@@ -35,6 +35,7 @@
 #include "kernels.h"
 #include "metrics.h"
 #include "precode.h"
+#include "scale.h"
 
 using namespace cairo;
 
@@ -214,6 +215,11 @@ struct cairo_ctx {
   // one.  pend_hpitch: the pitch of a host source still to upload (flush).
   uint8_t pend_fmt[kMaxBatch] = {};
   uint32_t pend_pitch[kMaxBatch] = {}, pend_hpitch[kMaxBatch] = {};
+  // A scaled frame (cairo_ctx_submit_scaled) is a device frame whose f.rgb is
+  // its staging slot, tight; its source and geometry wait here for the launch,
+  // whose k_scale_batch fills the slot before the convert reads it.
+  bool pend_scaled[kMaxBatch] = {};
+  ScaleFrame pend_scale[kMaxBatch] = {};
   int npend = 0;
   int last_slot = -1;  // slot of the last launched frame
   uint32_t last_epoch = 0;  // and its epoch (the tag of its inter records)
@@ -657,6 +663,25 @@ int flush(cairo_ctx* c) {
                       hipMemcpyHostToDevice, st));
   }
   if (tb) CK(hipEventRecord(tb->ev[0], st));
+  // Scaled frames: one k_scale_batch fills their staging slots before the
+  // convert reads them.  A launch without one enqueues nothing here.  A slot's
+  // previous frame may have been converted on the other launch stream (a
+  // ticket may be released unwaited): wait for that convert (rgb_read).
+  {
+    ScaleArgs sa;
+    sa.dw = (int)c->w, sa.dh = (int)c->h, sa.nframes = 0, sa.reserved = 0;
+    for (int i = 0; i < e.nframes; i++) {
+      if (!c->pend_scaled[i]) continue;
+      Stage& s = c->st[c->pend[i].slot];
+      if (s.rgb_pending) {
+        CK(hipStreamWaitEvent(st, s.rgb_read, 0));
+        s.rgb_pending = false;
+      }
+      sa.f[sa.nframes++] = c->pend_scale[i];
+      c->pend_scaled[i] = false;
+    }
+    if (sa.nframes) CK(launch_scale_batch(sa, st));
+  }
   // A launch of tight RGB24 frames keeps k_convert_batch, whose behaviour
   // beside the running launch is measured; any other
   // layout in the launch takes all of its frames through k_convert_fmt_batch.
@@ -1132,12 +1157,26 @@ int cairo_ctx_busy_intervals(cairo_ctx* c, double* out, int cap, int* n) {
 
 // cairo_ctx_submit (RGB24, tight) and cairo_ctx_submit_fmt.  check_range: an
 // on-device frame must lie, with all its bytes, inside one allocation.
+// With a source description (cairo_ctx_submit_scaled) rgb is a device frame of
+// the source's size and pitch is the source's: the frame is recorded as a
+// device frame whose f.rgb is its staging slot, tight, which the launch's
+// k_scale_batch fills from the source (flush).
 static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch, bool check_range,
-                        uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
+                        uint32_t index, uint32_t type, uint32_t quality, int* ticket,
+                        const cairo_source* scaled = nullptr) {
   if (!c || !rgb || !ticket || quality < 1 || quality > 31 || type > 1) return kInvalidArg;
   uint64_t frame_bytes = 0;
   uint32_t tight = 0;
-  if (cairo_frame_layout(fmt, c->w, c->h, pitch, &frame_bytes, &tight) != kSuccess) return kInvalidArg;
+  ScaleFrame plan{};
+  if (scaled) {
+    // (the scaler's grid has a row per plane row: at most 65535)
+    if (2ull * c->h > 65535 || scale_plan(fmt, pitch, scaled, c->w, c->h, rgb, nullptr, &plan) != kSuccess ||
+        cairo_frame_layout(fmt, scaled->width, scaled->height, pitch, &frame_bytes, nullptr) != kSuccess ||
+        cairo_frame_layout(fmt, c->w, c->h, 0, nullptr, &tight) != kSuccess)
+      return kInvalidArg;
+  } else if (cairo_frame_layout(fmt, c->w, c->h, pitch, &frame_bytes, &tight) != kSuccess) {
+    return kInvalidArg;
+  }
   std::lock_guard<std::mutex> lk(c->mu);
   CK(hipSetDevice(c->device));
   const int t = c->next_ticket;
@@ -1151,8 +1190,12 @@ static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int
     hipPointerAttribute_t pa;
     if (hipPointerGetAttributes(&pa, rgb) != hipSuccess || pa.type != hipMemoryTypeDevice || pa.device != c->device) {
       (void)hipGetLastError();
-      fprintf(stderr, "[cairo_amd] submit: rgb_on_device but %p is not device memory of device %d\n", (const void*)rgb,
-              c->device);
+      if (scaled)
+        fprintf(stderr, "[cairo_amd] submit_scaled: the source %p is not device memory of device %d (a host source is "
+                "not scaled: upload it once and submit the device frame)\n", (const void*)rgb, c->device);
+      else
+        fprintf(stderr, "[cairo_amd] submit: rgb_on_device but %p is not device memory of device %d\n",
+                (const void*)rgb, c->device);
       return kInvalidArg;
     }
     if (check_range) {  // a wrong pitch is refused here, not found as a read past the buffer
@@ -1162,16 +1205,22 @@ static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int
           (uint64_t)((const uint8_t*)rgb - (const uint8_t*)base) + frame_bytes > (uint64_t)size) {
         (void)hipGetLastError();
         fprintf(stderr, "[cairo_amd] submit: a format %d frame with pitch %u (%llu bytes) at %p does not fit its allocation\n",
-                fmt, pitch ? pitch : tight, (unsigned long long)frame_bytes, (const void*)rgb);
+                fmt, scaled ? plan.pitch : (pitch ? pitch : tight), (unsigned long long)frame_bytes, (const void*)rgb);
         return kInvalidArg;
       }
     }
   }
   FrameDesc& f = c->pend[c->npend];
   c->pend_fmt[c->npend] = (uint8_t)fmt;
-  c->pend_pitch[c->npend] = rgb_on_device && pitch ? pitch : tight;  // a host frame is staged tight
+  c->pend_pitch[c->npend] = rgb_on_device && pitch && !scaled ? pitch : tight;  // a host frame is staged tight
   c->pend_hpitch[c->npend] = pitch;
-  if (rgb_on_device) {
+  c->pend_scaled[c->npend] = scaled != nullptr;
+  if (scaled) {  // scaled into the slot at launch, tight
+    f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
+    f.host_rgb = nullptr;
+    plan.dst = const_cast<uint8_t*>(f.rgb);
+    c->pend_scale[c->npend] = plan;
+  } else if (rgb_on_device) {
     f.rgb = rgb;
     f.host_rgb = nullptr;
   } else {  // the caller keeps it valid until wait
@@ -1247,6 +1296,12 @@ int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32
 int cairo_ctx_submit_fmt(cairo_ctx* c, const uint8_t* frame, int on_device, int fmt, uint32_t pitch, uint32_t index,
                          uint32_t type, uint32_t quality, int* ticket) {
   return submit_frame(c, frame, on_device, fmt, pitch, true, index, type, quality, ticket);
+}
+
+int cairo_ctx_submit_scaled(cairo_ctx* c, const uint8_t* frame, int fmt, uint32_t pitch, const cairo_source* src,
+                            uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
+  if (!src) return kInvalidArg;
+  return submit_frame(c, frame, 1, fmt, pitch, true, index, type, quality, ticket, src);
 }
 
 static const char* timeout_kind_name(int k) {
@@ -1426,6 +1481,7 @@ static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef,
   frame_links(c, f, t);
   f.host_table = reinterpret_cast<const BlockDesc*>(table);
   f.host_coef = coef;
+  c->pend_scaled[0] = false;
   c->npend = 1;
   s.busy = true;
   s.launched = false;

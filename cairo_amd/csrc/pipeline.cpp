@@ -238,9 +238,10 @@ int cairo_stream_create(cairo_ctx* ctx, int threads, cairo_stream** out) {
   return kSuccess;
 }
 
-// cairo_stream_submit (fmt < 0: cairo_ctx_submit) and cairo_stream_submit_fmt.
+// cairo_stream_submit (fmt < 0: cairo_ctx_submit), cairo_stream_submit_fmt and,
+// with a source description, cairo_stream_submit_scaled.
 static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch,
-                         uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
+                         const cairo_source* src, uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (!s || !rgb || !ticket) return kInvalidArg;
   const int t = s->next;
   {
@@ -255,8 +256,9 @@ static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device,
     });
   }
   int tk = -1;
-  const int r = fmt < 0 ? cairo_ctx_submit(s->ctx, rgb, rgb_on_device, index, type, quality, &tk)
-                        : cairo_ctx_submit_fmt(s->ctx, rgb, rgb_on_device, fmt, pitch, index, type, quality, &tk);
+  const int r = src       ? cairo_ctx_submit_scaled(s->ctx, rgb, fmt, pitch, src, index, type, quality, &tk)
+                : fmt < 0 ? cairo_ctx_submit(s->ctx, rgb, rgb_on_device, index, type, quality, &tk)
+                          : cairo_ctx_submit_fmt(s->ctx, rgb, rgb_on_device, fmt, pitch, index, type, quality, &tk);
   if (r) return r;
   {
     std::lock_guard<std::mutex> lk(s->m);
@@ -277,13 +279,19 @@ static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device,
 
 int cairo_stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, uint32_t index,
                         uint32_t type, uint32_t quality, int* ticket) {
-  return stream_submit(s, rgb, rgb_on_device, -1, 0, index, type, quality, ticket);
+  return stream_submit(s, rgb, rgb_on_device, -1, 0, nullptr, index, type, quality, ticket);
 }
 
 int cairo_stream_submit_fmt(cairo_stream* s, const uint8_t* frame, int on_device, int fmt, uint32_t pitch,
                             uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (fmt < 0) return kInvalidArg;
-  return stream_submit(s, frame, on_device, fmt, pitch, index, type, quality, ticket);
+  return stream_submit(s, frame, on_device, fmt, pitch, nullptr, index, type, quality, ticket);
+}
+
+int cairo_stream_submit_scaled(cairo_stream* s, const uint8_t* frame, int fmt, uint32_t pitch, const cairo_source* src,
+                               uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
+  if (fmt < 0 || !src) return kInvalidArg;
+  return stream_submit(s, frame, 1, fmt, pitch, src, index, type, quality, ticket);
 }
 
 int cairo_stream_collect(cairo_stream* s, int ticket, uint8_t* out, uint64_t out_bytes,

@@ -46,7 +46,10 @@ extern "C" {
  *      only: cairo_ctx_set_metrics, cairo_ctx_frame_metrics,
  *      cairo_ctx_fetch_recon[_planes], cairo_stream_frame_metrics,
  *      cairo_kat_metrics, evx_encoder_set_metrics / _last_metrics.  Nothing
- *      existing changes, so the version stays: detect them by their symbols. */
+ *      existing changes, so the version stays: detect them by their symbols.
+ *   4  (unchanged) the scaled submit adds entry points only as well:
+ *      cairo_source_size, cairo_scale_check, cairo_ctx_submit_scaled,
+ *      cairo_stream_submit_scaled, cairo_kat_scale. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -134,6 +137,64 @@ CAIRO_API int cairo_ctx_submit(cairo_ctx *ctx, const uint8_t *rgb, int rgb_on_de
 CAIRO_API int cairo_ctx_submit_fmt(cairo_ctx *ctx, const uint8_t *frame, int on_device, int fmt,
                                    uint32_t pitch, uint32_t index, uint32_t type, uint32_t quality,
                                    int *ticket);
+
+/* ---- scaled submit ---------------------------------------
+ * One source frame in device memory feeds contexts of several sizes (the 4K
+ * master and its 1080p and 720p renditions): each context reads it in place
+ * and scales it to its own width x height on the GPU, before its convert.
+ *
+ * The rule is an area average in exact integers, applied to every 8-bit sample
+ * plane as the format stores it: R, G and B of RGB24 / BGR24; Y8, U8 and V8 of
+ * I420 / NV12, the chroma planes at half size in both axes.  Per axis, with S
+ * samples of the source region and D output samples (chroma: both halved),
+ * g = gcd(S, D), L = S / g, P = D / g: output sample o covers the units
+ * [o L, (o + 1) L), source sample s the units [s P, (s + 1) P), and w(o, s) is
+ * the length of their overlap (for one o the weights sum to L).  Then
+ *   out(ox, oy) = (sum_sy sum_sx wy(oy, sy) wx(ox, sx) src(sx, sy)
+ *                  + ((Lx Ly) >> 1)) / (Lx Ly)                  (floor division)
+ * with no intermediate rounding.  S == D is a copy; an exact 2:1 is the mean
+ * of a 2x2 block, halves rounded up.  The result is a tight frame of the same
+ * format at the context's size, and everything downstream is what a tight
+ * frame of that format gets: a scaled submit produces exactly the bits of
+ * submitting the scaled frame.
+ *
+ * Constraints (EVX_ERROR_INVALID_ARGS): source width, height and the four crop
+ * values even; the crop inside the source; D <= S <= 8 D on each axis
+ * (downscale or copy, at most 8:1); 255 Lx Ly < 2^31; a source of at most
+ * 32768 x 32768; reserved words 0.  The source must be device memory of the
+ * context's GPU: the staging slot it is scaled into holds a frame of the
+ * context's size, not a larger source, and uploading once and reading in place
+ * is the point, so a host source is refused. */
+typedef struct cairo_source {
+  uint32_t width, height;                  /* size of the source frame (even)               */
+  uint32_t crop_x, crop_y, crop_w, crop_h; /* region to scale; crop_w == 0 (then all four   */
+                                           /* are 0): the whole frame                       */
+  uint32_t reserved[2];                    /* 0                                             */
+} cairo_source;
+/* sizeof(cairo_source), for bindings. */
+CAIRO_API int cairo_source_size(void);
+/* Validity of scaling src (format fmt, row pitch `pitch` of the source, 0:
+ * tight) to dst_w x dst_h; no device needed. */
+CAIRO_API int cairo_scale_check(int fmt, uint32_t pitch, const cairo_source *src, uint32_t dst_w,
+                                uint32_t dst_h);
+/* cairo_ctx_submit_fmt of the frame that scaling src to the context's size
+ * gives.  frame is device memory of this context's GPU, inside one allocation
+ * with all cairo_frame_layout(fmt, src->width, src->height, pitch) bytes, at
+ * any byte alignment; it is read when the frame's batch launches and must stay
+ * valid until the frame's wait.  A launch may mix scaled and unscaled frames,
+ * source sizes, crops and formats.  A refused submit takes no ticket. */
+CAIRO_API int cairo_ctx_submit_scaled(cairo_ctx *ctx, const uint8_t *frame, int fmt, uint32_t pitch,
+                                      const cairo_source *src, uint32_t index, uint32_t type,
+                                      uint32_t quality, int *ticket);
+/* Known-answer check of the scaling kernel on host buffers, without a context
+ * or the engine.  out holds the tight dst_w x dst_h frame followed by
+ * CAIRO_KAT_SCALE_GUARD more bytes; all of it is uploaded first, so bytes the
+ * kernel must not touch (the guard) can be checked.  The device copy of frame
+ * keeps frame's address modulo 4, so a misaligned source can be checked. */
+#define CAIRO_KAT_SCALE_GUARD 64
+CAIRO_API int cairo_kat_scale(int fmt, uint32_t pitch, const cairo_source *src, const uint8_t *frame,
+                              uint32_t dst_w, uint32_t dst_h, uint8_t *out, int device);
+
 /* Wait until the frame's block table and coefficients are host-visible. */
 CAIRO_API int cairo_ctx_wait(cairo_ctx *ctx, int ticket, cairo_frame_result *out);
 /* The decoder's hot path (decode_slice + deblock + convert_image,
@@ -452,6 +513,10 @@ CAIRO_API int cairo_stream_submit(cairo_stream *s, const uint8_t *rgb, int rgb_o
 CAIRO_API int cairo_stream_submit_fmt(cairo_stream *s, const uint8_t *frame, int on_device, int fmt,
                                       uint32_t pitch, uint32_t index, uint32_t type, uint32_t quality,
                                       int *ticket);
+/* cairo_stream_submit for a scaled frame (cairo_ctx_submit_scaled). */
+CAIRO_API int cairo_stream_submit_scaled(cairo_stream *s, const uint8_t *frame, int fmt, uint32_t pitch,
+                                         const cairo_source *src, uint32_t index, uint32_t type,
+                                         uint32_t quality, int *ticket);
 /* Wait for the frame's payload and append it at bit *bit_pos of out
  * (out_bytes capacity, LSB-first; out == NULL only advances *bit_pos).  If it
  * does not fit, returns EVX_ERROR_CAPACITY_LIMIT (7) and keeps the payload:
