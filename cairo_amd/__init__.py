@@ -504,7 +504,8 @@ class Context:
                    "subpel_select", "db_inputs", "db_filter", "db_write",
                    "search_passes", "search_mbs_2pass", "search_mbs_3pass", "search_mbs_4pass",
                    "coder_xform_copy", "coder_copy_mbs", "coder_xform_coded", "coder_coded_mbs",
-                   "helper_carry", "carry_bytes")
+                   "helper_carry", "carry_bytes",
+                   "coder_prologue_fresh", "coder_prologue_records", "helper_group_start")
 
     def read_acct(self, reset: bool = False) -> dict:
         """Engine time accounting (set_debug(32) on a CAIRO_ACCT=1 build): 10 ns

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "evx_defs.h"
@@ -112,7 +113,7 @@ enum TimeoutKind : int32_t {
 #ifndef CAIRO_ACCT
 #define CAIRO_ACCT 0
 #endif
-constexpr int kAcctShards = 64, kAcctWords = 50;
+constexpr int kAcctShards = 64, kAcctWords = 53;
 struct Acct {
   // row coders
   static constexpr int kCoderTasks = 0, kCoderTotal = 1, kCoderGroupWait = 2, kCoderWindow = 3, kCoderSearch = 4,
@@ -152,6 +153,12 @@ struct Acct {
   // load to the last store issued (its acknowledgements are waited for
   // behind the window's DMA), and the bytes carried
   static constexpr int kHelperCarry = 48, kCarryBytes = 49;
+  // the prologues, where the frame view's fields are fetched one scalar load
+  // and one wait at a time: the coder's macroblock start to
+  // the fresh granule's load issued, from there to the record loads issued
+  // (inside a group; at a group start they go out after the search), and a
+  // searched inter task's entry to its first window DMA
+  static constexpr int kCoderProFresh = 50, kCoderProRecords = 51, kHelperGroupStart = 52;
 };
 
 // Frames per engine launch.
@@ -196,66 +203,114 @@ struct FrameDesc {
 // Per-frame view of the engine's state, built by the host for every frame of
 // a launch and read by the kernels from device memory (never copied into
 // private memory).
-struct FrameArgs {
+//
+// Layout: the fields a phase of the kernels reads together are contiguous, in
+// blocks aligned to 64 bytes, so that a phase fetches its block with one wide
+// scalar load and one wait (kernels.hip view_block) instead of a
+// load and a wait per field.  The host fills the fields by name
+// (make_frame_view) and copies views in 16-byte chunks; the offsets the
+// kernels' block reads rest on are asserted below the struct.
+struct alignas(64) FrameArgs {
+  // ---- block 0 (64 bytes): the row coder's macroblock start ----
   int wa, ha;          // frame size aligned to 16 (evx1enc.cpp:79-80)
-  int w, h;            // nominal frame size (RGB input)
   int wmb, hmb;        // macroblocks per row / column
-  int ring;            // R = ring size (EVX_REFERENCE_FRAME_COUNT)
-  int index, inter, quality;
-  int decode;          // decode mode (FrameDesc::decode): table and coef are inputs
   uint32_t epoch;
+  int nrec;            // inter records per macroblock: ring - 1 on an inter frame, 0 otherwise
+  BlockDesc* inter_desc;  // [(off-1)*mbs + mb]: two tagged granules (desc, SAD) per record
   PlaneSet in;         // input_cache of this frame
-  PlaneSet coef;       // output_cache of this frame (persistent semantics: copy MBs carry coef_prev)
-  PlaneSet coef_prev;  // output_cache of the previous frame
+  uint64_t* granules;  // [mbs * kGranuleStride]
+  // ---- block 1 (two halves of 32 bytes): window prefetch; group start ----
+  // The rows below an intra search: frame index-R's deblocked output (zeros
+  // for the first R frames).  The reference reuses that slot in place, so this
+  // equals recon[0] whenever the group's slot arithmetic does too.
+  PlaneSet stale;
+  int ring;            // R = ring size (EVX_REFERENCE_FRAME_COUNT)
+  int pad1;
+  int32_t* inter_done; // [hmb][ng] inter-search tasks finished
+  int ng;              // inter-search groups (4 MBs) per row
+  // 1: the cross-frame buffers are shared with other devices or processes (a
+  // frame-interleaved group): progress words are stored and polled at system
+  // scope, with a system-scope release before each store and a system-scope
+  // acquire after each wait on another frame's data.
+  int sys;
+  int nref;            // inter-search tasks per group (references; 1 carrier task for intra frames)
+  int inter;           // 0 intra, 1 inter (FrameDesc::inter, resolved: make_frame_view)
+  uint64_t* acct;      // diagnostic time accounting (EngineArgs::acct)
+  // ---- block 2 (128 bytes): classification and prediction ----
   // Reconstruction buffers: [0] this frame's (written only by its deblock),
   // [off] = frame index-off for off = 1..R-1 (inter references; zero images
   // before the stream start).  In one context these are ring slots
   // (index-off) % R (common.cpp:192-195).
   PlaneSet recon[kMaxRing];
-  // The rows below an intra search: frame index-R's deblocked output (zeros
-  // for the first R frames).  The reference reuses that slot in place, so this
-  // equals recon[0] whenever the group's slot arithmetic does too.
-  PlaneSet stale;
-  // Mirrors of recon[0] on the members that read this frame (a group on
-  // several devices or processes): the deblock stores every written word to
-  // each of them as well, before the progress word that declares it final,
-  // so the readers' searches read local memory instead of a peer's over xGMI.
-  PlaneSet push[kMaxPush];
-  int npush;
   BlockDesc* table;    // [wmb*hmb]
-  BlockDesc* inter_desc;  // [(off-1)*mbs + mb]: two tagged granules (desc, SAD) per record
-  // (unused: holds the field offsets -- and so the kernels' scalar-load
-  // merging of this struct -- as measured; dropping it cost 1.3 % at 4K)
-  void* reserved0;
-  uint64_t* granules;  // [mbs * kGranuleStride]
-  int32_t* err;        // batch error word (a bounded wait timed out)
-  int32_t* sticky;     // TimeoutInfo words, never cleared by a launch (reported by the host)
+  int quality;
+  int decode;          // decode mode (FrameDesc::decode): table and coef are inputs
+  int index;
   int member;          // group rank of the encoding context (0 alone): timeout diagnostics
-  int inject;          // test hook: 1 = row helpers of row min(1, hmb-1) record an injected timeout
-  int ng;              // inter-search groups (4 MBs) per row
-  int nref;            // inter-search tasks per group (references; 1 carrier task for intra frames)
-  int32_t* inter_done; // [hmb][ng] inter-search tasks finished
+  int32_t* err;        // batch error word (a bounded wait timed out)
+  // ---- block 3 (64 bytes): stores and publish, deblock chunk ----
+  PlaneSet coef;       // output_cache of this frame (persistent semantics: copy MBs carry coef_prev)
+  PlaneSet coef_prev;  // output_cache of the previous frame
   // Deblock progress per MB row, tagged: (epoch << 32) | final luma columns.
   // Frame epochs of a stream are consecutive, so the previous frame's words
   // are compared against (epoch - 1) << 32 | need; a staging slot's words are
   // never cleared between frames (a later frame's larger tag also means the
   // earlier frame is final there), so no launch ordering guards them.
   uint64_t* progress;             // [hmb] this frame's
+  int db_shift;        // deblock chunk width, log2 luma columns (4..6: 1, 2 or 4 macroblocks)
+  int npush;
+  // ---- block 4 (64 bytes): helper group start and carry ----
   const uint64_t* prev_progress;  // [hmb] the previous frame's (nullptr: none)
   // [hmb] frame index-2's (nullptr: none): the searches of the older
   // references (offsets 2..R-1) wait on it instead of the previous frame
   const uint64_t* prev2_progress;
-  // 1: the cross-frame buffers are shared with other devices or processes (a
-  // frame-interleaved group): progress words are stored and polled at system
-  // scope, with a system-scope release before each store and a system-scope
-  // acquire after each wait on another frame's data.
-  int sys;
-  int db_shift;        // deblock chunk width, log2 luma columns (4..6: 1, 2 or 4 macroblocks)
-  uint64_t* stamps;    // diagnostic (nullptr = off)
-  uint64_t* acct;      // diagnostic time accounting (EngineArgs::acct)
+  int32_t* sticky;     // TimeoutInfo words, never cleared by a launch (reported by the host)
   uint64_t* istamps;   // diagnostic: per (row, group) of the inter search, kIStamps stamps (see kernels.hip)
   const uint8_t* rgb;  // RGB888 input, pitch 3*w (device memory)
+  int inject;          // test hook: 1 = row helpers of row min(1, hmb-1) record an injected timeout
+  int w, h;            // nominal frame size (RGB input)
+  int pad0;
+  uint64_t* stamps;    // diagnostic (nullptr = off)
+  // ---- block 5 (128 bytes): the deblock's mirrors ----
+  // Mirrors of recon[0] on the members that read this frame (a group on
+  // several devices or processes): the deblock stores every written word to
+  // each of them as well, before the progress word that declares it final,
+  // so the readers' searches read local memory instead of a peer's over xGMI.
+  PlaneSet push[kMaxPush];
 };
+// The blocks (kernels.hip view_block reads them whole) and the size the
+// convert kernels' 16-byte view copy and the view arrays rest on.
+struct ViewLayout {
+  static constexpr size_t kCoderStart = 0, kStale = 64, kGroup = 96, kPredict = 128, kPublish = 256, kHelper = 320,
+                          kPush = 384, kSize = 512;
+};
+static_assert(offsetof(FrameArgs, wa) == ViewLayout::kCoderStart && offsetof(FrameArgs, ha) == 4 &&
+                  offsetof(FrameArgs, wmb) == 8 && offsetof(FrameArgs, hmb) == 12 && offsetof(FrameArgs, epoch) == 16 && offsetof(FrameArgs, nrec) == 20 &&
+                  offsetof(FrameArgs, inter_desc) == 24 && offsetof(FrameArgs, in) == 32 &&
+                  offsetof(FrameArgs, granules) == 56,
+              "FrameArgs block 0: the coder's macroblock start");
+static_assert(offsetof(FrameArgs, stale) == ViewLayout::kStale && offsetof(FrameArgs, ring) == 88 &&
+                  offsetof(FrameArgs, inter_done) == ViewLayout::kGroup && offsetof(FrameArgs, ng) == 104 &&
+                  offsetof(FrameArgs, sys) == 108 && offsetof(FrameArgs, nref) == 112 &&
+                  offsetof(FrameArgs, inter) == 116 && offsetof(FrameArgs, acct) == 120,
+              "FrameArgs block 1: window prefetch; group start");
+static_assert(offsetof(FrameArgs, recon) == ViewLayout::kPredict && offsetof(FrameArgs, table) == 224 &&
+                  offsetof(FrameArgs, quality) == 232 && offsetof(FrameArgs, decode) == 236 &&
+                  offsetof(FrameArgs, index) == 240 && offsetof(FrameArgs, member) == 244 &&
+                  offsetof(FrameArgs, err) == 248,
+              "FrameArgs block 2: classification and prediction");
+static_assert(offsetof(FrameArgs, coef) == ViewLayout::kPublish && offsetof(FrameArgs, coef_prev) == 280 &&
+                  offsetof(FrameArgs, progress) == 304 && offsetof(FrameArgs, db_shift) == 312 &&
+                  offsetof(FrameArgs, npush) == 316,
+              "FrameArgs block 3: stores and publish, deblock chunk");
+static_assert(offsetof(FrameArgs, prev_progress) == ViewLayout::kHelper && offsetof(FrameArgs, prev2_progress) == 328 &&
+                  offsetof(FrameArgs, sticky) == 336 && offsetof(FrameArgs, istamps) == 344 &&
+                  offsetof(FrameArgs, rgb) == 352 && offsetof(FrameArgs, inject) == 360 &&
+                  offsetof(FrameArgs, w) == 364 && offsetof(FrameArgs, h) == 368 && offsetof(FrameArgs, stamps) == 376,
+              "FrameArgs block 4: helper group start and carry");
+static_assert(offsetof(FrameArgs, push) == ViewLayout::kPush && sizeof(FrameArgs) == ViewLayout::kSize &&
+                  alignof(FrameArgs) == 64 && sizeof(FrameArgs) % sizeof(uint4) == 0,
+              "FrameArgs block 5 and the size (views are copied in 16-byte chunks)");
 
 // Build the view of frame j of a launch (host side; kernels.h layout rules).
 struct EngineArgs;

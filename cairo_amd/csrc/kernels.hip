@@ -172,10 +172,10 @@ __device__ __forceinline__ int fresh(int v) {
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Diagnostic timestamp (100 MHz constant clock) of phase k of macroblock mb.
-__device__ __forceinline__ void stamp(FA& a, int mb, int k) {
-  if (a.stamps && threadIdx.x == 0)
-    a.stamps[(size_t)mb * kStampPhases + k] = __builtin_amdgcn_s_memrealtime();
+__device__ __forceinline__ void stamp(uint64_t* stamps, int mb, int k) {
+  if (stamps && threadIdx.x == 0) stamps[(size_t)mb * kStampPhases + k] = __builtin_amdgcn_s_memrealtime();
 }
+__device__ __forceinline__ void stamp(FA& a, int mb, int k) { stamp(a.stamps, mb, k); }
 
 // Time accounting (kernels.h Acct; CAIRO_ACCT=1 builds with cairo_ctx_set_debug
 // 32): thread 0 adds 10 ns ticks to its workgroup's shard (posted atomics).
@@ -185,6 +185,17 @@ __device__ __forceinline__ void acct_add(uint64_t* acct, int k, uint64_t v) {
     __hip_atomic_fetch_add(&acct[(blockIdx.x & (kAcctShards - 1)) * kAcctWords + k], v, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
 }
+
+// Assembly comments that bracket a stretch of a kernel for tools/smem_counts.py
+// (-DCAIRO_ASM_MARKS=1 builds; a product build emits nothing).
+#ifndef CAIRO_ASM_MARKS
+#define CAIRO_ASM_MARKS 0
+#endif
+#if CAIRO_ASM_MARKS
+#define ASM_MARK(s) asm volatile("; cairo-mark " s)
+#else
+#define ASM_MARK(s) ((void)0)
+#endif
 
 // Deblock progress words (kernels.h FrameArgs::progress): tag a column count
 // with the frame's epoch; relaxed agent-scope 64-bit loads.
@@ -279,8 +290,10 @@ __device__ __forceinline__ void gran_st(uint64_t* p, uint64_t v) {
 // The record granule p of frame a (tagged inter records, kernels.h
 // pack_inter_desc), given a first load g: re-polls until the tag is the
 // frame's epoch; bounded (report_timeout: kind records, on = the macroblock).
-__device__ __forceinline__ uint32_t rec_settle(FA& a, const uint64_t* p, uint64_t g, int row, int mb) {
-  if ((uint32_t)(g >> 32) == a.epoch) return (uint32_t)g;
+// epoch = a.epoch, from the caller's block read of the view (view_block); the
+// re-poll path (cold) reads the view's fields itself.
+__device__ __forceinline__ uint32_t rec_settle(FA& a, uint32_t epoch, const uint64_t* p, uint64_t g, int row, int mb) {
+  if ((uint32_t)(g >> 32) == epoch) return (uint32_t)g;
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
   for (;;) {
     __builtin_amdgcn_s_sleep(kWaitSleep);
@@ -300,12 +313,16 @@ __device__ __forceinline__ uint32_t rec_settle(FA& a, const uint64_t* p, uint64_
   }
   return (uint32_t)g;
 }
+__device__ __forceinline__ uint32_t rec_settle(FA& a, const uint64_t* p, uint64_t g, int row, int mb) {
+  return rec_settle(a, a.epoch, p, g, row, mb);
+}
 
 // Data of granule p of frame a, given a first load g: re-polls until the tag
 // is the frame's epoch.  Bounded like every wait (the error word ends every
 // other wait too); row = the waiting task's row, for the timeout record.
-__device__ __forceinline__ uint32_t gran_settle(FA& a, const uint64_t* p, uint64_t g, int row) {
-  if ((uint32_t)(g >> 32) == a.epoch) return (uint32_t)g;
+// (epoch: as for rec_settle)
+__device__ __forceinline__ uint32_t gran_settle(FA& a, uint32_t epoch, const uint64_t* p, uint64_t g, int row) {
+  if ((uint32_t)(g >> 32) == epoch) return (uint32_t)g;
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
   for (;;) {
     __builtin_amdgcn_s_sleep(kGranSleep);
@@ -325,6 +342,9 @@ __device__ __forceinline__ uint32_t gran_settle(FA& a, const uint64_t* p, uint64
   }
   return (uint32_t)g;
 }
+__device__ __forceinline__ uint32_t gran_settle(FA& a, const uint64_t* p, uint64_t g, int row) {
+  return gran_settle(a, a.epoch, p, g, row);
+}
 
 // p, opaque to the optimiser: the frame view's fields are re-read (scalar
 // loads that hit the scalar cache) in every macroblock instead of being
@@ -333,6 +353,61 @@ __device__ __forceinline__ FA* opaque_view(FA* p) {
   uint64_t v = (uint64_t)p;
   asm volatile("" : "+s"(v));
   return (FA*)v;
+}
+
+// A 32- or 64-byte block of a view (kernels.h ViewLayout) read as one vector
+// from the constant address space: the block's scalar loads go out back to
+// back behind ONE wait (the compiler narrows the read to the fields that are
+// used, e.g. dwordx4 + dwordx2 + dwordx8 + dwordx2 for block 0), instead of a
+// load and a wait per field and basic block.  Call it right after opaque_view,
+// before the phase's first use.  The mirror structs name a block's fields;
+// their offsets are asserted against FrameArgs.  Blocks are read where they
+// are used and again after the searches, never kept live across them: the
+// values would spill (DESIGN.md §4.11 lists the variants that did).
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+struct ViewCoderStart {  // block 0
+  int wa, ha, wmb, hmb;
+  uint32_t epoch;
+  int nrec;
+  BlockDesc* inter_desc;
+  PlaneSet in;
+  uint64_t* granules;
+  static constexpr size_t kAt = ViewLayout::kCoderStart;
+};
+struct ViewStale {  // block 1, first half
+  PlaneSet stale;
+  int ring, pad1;
+  static constexpr size_t kAt = ViewLayout::kStale;
+};
+struct ViewGroup {  // block 1, second half
+  int32_t* inter_done;
+  int ng, sys, nref, inter;
+  uint64_t* acct;
+  static constexpr size_t kAt = ViewLayout::kGroup;
+};
+#define VIEW_FIELD_AT(B, f) (offsetof(B, f) + B::kAt == offsetof(FrameArgs, f))
+static_assert(sizeof(ViewCoderStart) == 64 && VIEW_FIELD_AT(ViewCoderStart, wa) && VIEW_FIELD_AT(ViewCoderStart, ha) &&
+                  VIEW_FIELD_AT(ViewCoderStart, wmb) && VIEW_FIELD_AT(ViewCoderStart, hmb) &&
+                  VIEW_FIELD_AT(ViewCoderStart, epoch) && VIEW_FIELD_AT(ViewCoderStart, nrec) &&
+                  VIEW_FIELD_AT(ViewCoderStart, inter_desc) && VIEW_FIELD_AT(ViewCoderStart, in) &&
+                  VIEW_FIELD_AT(ViewCoderStart, granules),
+              "ViewCoderStart mirrors FrameArgs block 0");
+static_assert(VIEW_FIELD_AT(ViewStale, stale) && VIEW_FIELD_AT(ViewStale, ring), "ViewStale mirrors FrameArgs block 1");
+static_assert(VIEW_FIELD_AT(ViewGroup, inter_done) && VIEW_FIELD_AT(ViewGroup, ng) && VIEW_FIELD_AT(ViewGroup, sys) &&
+                  VIEW_FIELD_AT(ViewGroup, nref) && VIEW_FIELD_AT(ViewGroup, inter) && VIEW_FIELD_AT(ViewGroup, acct),
+              "ViewGroup mirrors FrameArgs block 1");
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+template <class B>
+__device__ __forceinline__ B view_block(FA* p) {
+  static_assert((sizeof(B) == 64 || sizeof(B) == 32) && B::kAt % sizeof(B) == 0, "one aligned 32- or 64-byte scalar load");
+  typedef const __attribute__((address_space(4))) char cchar;
+  if constexpr (sizeof(B) == 64) {
+    typedef const __attribute__((address_space(4))) u32x16 cvec;
+    return __builtin_bit_cast(B, *(cvec*)((cchar*)p + B::kAt));
+  } else {
+    typedef const __attribute__((address_space(4))) u32x8 cvec;
+    return __builtin_bit_cast(B, *(cvec*)((cchar*)p + B::kAt));
+  }
 }
 
 // Dequeue the next task index for this workgroup (uniform result).
@@ -993,16 +1068,16 @@ __device__ __forceinline__ void group_source(FA& a, int r, int g, InterLds& L) {
 // dst + lane x 16).  The source planes do not change during a launch.  Lands
 // behind wave 0's next vmcnt wait; readable by every wave after the barrier
 // that follows it.
-__device__ __forceinline__ void src_dma(FA& a, int x, int r, int16_t* dst) {
+__device__ __forceinline__ void src_dma(const PlaneSet& in, int wa, int x, int r, int16_t* dst) {
   const int lane = threadIdx.x;
   if (lane >= 48) return;
-  const PlaneSet in = planes(a.in);
   const int px = x * kMB, py = r * kMB;
-  const int16_t* gsrc = lane < 32 ? in.y + (size_t)(py + (lane >> 1)) * a.wa + px + 8 * (lane & 1)
+  const int16_t* gsrc = lane < 32 ? in.y + (size_t)(py + (lane >> 1)) * wa + px + 8 * (lane & 1)
                                   : pick(in, 1 + ((lane - 32) >> 3)) +
-                                        (size_t)((py >> 1) + (lane & 7)) * (a.wa >> 1) + (px >> 1);
+                                        (size_t)((py >> 1) + (lane & 7)) * (wa >> 1) + (px >> 1);
   __builtin_amdgcn_global_load_lds((const void*)gsrc, (lds_void*)dst, 16, 0, 0);
 }
+__device__ __forceinline__ void src_dma(FA& a, int x, int r, int16_t* dst) { src_dma(planes(a.in), a.wa, x, r, dst); }
 
 // This lane's Px6 slice (px_from_planes layout) and its SrcRow (load_src_rows
 // layout, biased) of wave w's source macroblock, from L.src.
@@ -1130,6 +1205,8 @@ __device__ __forceinline__ bool carry_group(FA& a, int r, int g) {
 __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterLds& L, DbLds& D, DbState& st,
                                            int* flag, uint64_t* is, bool carried = false) {
   FA& a = *opaque_view(&a0);
+  ASM_MARK("group_start begin");
+  const uint64_t tg0 = acct_now();
   const int wave = uni(threadIdx.x >> 6);  // scalar: the acceptance replay runs on SGPRs
   const int x = 4 * g + wave;
   const bool valid = x < a.wmb;
@@ -1183,6 +1260,8 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
     const bool full = L.full != 0;  // workgroup-uniform
     acct_add(a.acct, Acct::kSearchedTasks, 1);
     acct_window(a.acct, 0, full ? kWinL : kLvl1Rows, 0, full ? kWinLW : kLvl1Cols);
+    acct_add(a.acct, Acct::kHelperGroupStart, acct_now() - tg0);
+    ASM_MARK("group_start end");
     // (the DMA's vmcnt(0) and barrier in here are also the carry's release:
     // every wave's carry stores, issued before its DMA, are acknowledged)
     stage_window(L.win, ref, a.wa, a.ha, ox, oy, 0, full ? kWinL : kLvl1Rows, 0, full ? kWinLW : kLvl1Cols);
@@ -2094,8 +2173,11 @@ __device__ __forceinline__ BlockDesc uni_desc(const BlockDesc& d) {
   return u;
 }
 
+__device__ __forceinline__ uint64_t* gran_at(uint64_t* granules, int wmb, int mbx, int mby, int k) {
+  return granules + (size_t)(mby * wmb + mbx) * kGranuleStride + k;
+}
 __device__ __forceinline__ uint64_t* gran_at(FA& a, int mbx, int mby, int k) {
-  return a.granules + (size_t)(mby * a.wmb + mbx) * kGranuleStride + k;
+  return gran_at(a.granules, a.wmb, mbx, mby, k);
 }
 
 // Store lane pairs (lane, lane^1) of an 8x8 block's int16 values as dwords
@@ -2123,11 +2205,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int grp = tid >> 4, gi = tid & 15;
   const int thr = (a.quality >> 2) + 1;
-  const PlaneSet cs = planes(a.stale);  // the stale rows below (frame index-R)
-  const uint32_t tag = a.epoch;
-  const int cw = a.wa >> 1;
   const int nblk = wave < 2 ? 2 : 1;  // wave w owns 8x8 blocks w and w+4
-  const int mbs = a.wmb * a.hmb;
   {
     const int py = by * kMB, oy = py - 48;
     if (!kDecode) {  // macroblock 0's source; later ones are staged a macroblock ahead
@@ -2135,12 +2213,19 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    for (int bx = 0; bx < a0.wmb; bx++) {
+    bool more = true;  // (the row's length from the macroblock's own read of the view)
+    for (int bx = 0; more; bx++) {
       FA* ap = opaque_view(&a0);
-      const int px = bx * kMB, mb = by * ap->wmb + bx;
+      ASM_MARK("mb_start begin");
+      // what the loads of this stretch need of the view: one block read
+      // behind one wait, so that the source DMA, the fresh
+      // granule's load and the record loads below all go out behind it
+      const ViewCoderStart vs = view_block<ViewCoderStart>(ap);
+      const uint64_t tp0 = acct_now();
+      const int px = bx * kMB, mb = by * vs.wmb + bx;
       trace(tr, 1, bx);
-      trace(tr, 2, (int)ap->epoch * 1000 + by);
-      stamp(*ap, mb, 0);
+      trace(tr, 2, (int)vs.epoch * 1000 + by);
+      stamp(ap->stamps, mb, 0);
       if (ap->stamps && tid == 0) ap->stamps[(size_t)mb * kStampPhases + 10] = __builtin_amdgcn_s_memtime();
       // The row above's fresh column block (bx+2, by-1): its first granule
       // load is issued before the group-start wait below, so that a granule
@@ -2148,10 +2233,11 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       // 64-bit load needs no acquire).
       // macroblock bx+1's source into LDS, in flight with the fresh granule
       // load below, whose wait covers it (the buffer was last read in bx-1)
-      if (!kDecode && bx + 1 < ap->wmb) src_dma(*ap, bx + 1, by, L.src[(bx + 1) & 1]);
-      const bool fresh_col = by > 0 && bx != 0 && bx + 2 < ap->wmb && tid < kGranulesPerMB;
-      const uint64_t* fresh_gp = fresh_col ? gran_at(*ap, bx + 2, by - 1, tid) : nullptr;
+      if (!kDecode && bx + 1 < vs.wmb) src_dma(vs.in, vs.wa, bx + 1, by, L.src[(bx + 1) & 1]);
+      const bool fresh_col = by > 0 && bx != 0 && bx + 2 < vs.wmb && tid < kGranulesPerMB;
+      const uint64_t* fresh_gp = fresh_col ? gran_at(vs.granules, vs.wmb, bx + 2, by - 1, tid) : nullptr;
       const uint64_t fresh_g = fresh_col ? gran_ld(fresh_gp) : 0;
+      const uint64_t tp1 = acct_now();
       // At a group start the coder needs the group's inter records, and every
       // cross-frame dependency they carry (the stale rows, references and
       // previous output_cache), only for the classification: the intra search
@@ -2165,18 +2251,20 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       // already, so their loads go out here, in flight with the fresh
       // granule's, instead of a round trip of their own after it (settled by
       // tag in load_inter).  At a group start, after the search.
-      const int nref = ap->inter ? ap->ring - 1 : 0;
+      const int nref = vs.nrec;
       uint64_t rg[kMaxRing - 1][2];
-      auto issue_records = [&]() {
+      auto issue_records = [&](const ViewCoderStart& g) {
 #pragma unroll
         for (int o = 0; o < kMaxRing - 1; o++) {
           if (o >= nref) break;
-          const uint64_t* r = (const uint64_t*)&ap->inter_desc[o * mbs + mb];
+          const uint64_t* r = (const uint64_t*)&g.inter_desc[o * (g.wmb * g.hmb) + mb];
           rg[o][0] = gran_ld(r);
           rg[o][1] = gran_ld(r + 1);
         }
       };
-      if (!early) issue_records();
+      if (!early) issue_records(vs);
+      acct_add(ap->acct, Acct::kCoderProFresh, tp1 - tp0);
+      if (!early) acct_add(ap->acct, Acct::kCoderProRecords, acct_now() - tp1);
 #ifdef CAIRO_ACCT_STORE_TAIL
       {  // diagnostic (tools builds): how long the previous macroblock's stores still take here
         const uint64_t ts = acct_now();
@@ -2191,8 +2279,8 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       // macroblock's record of reference 1 -- the helper's last search, after
       // its wait for the previous frame -- carries this frame's tag; otherwise
       // (intra and decoded frames: the helper's carrier) once inter_done says so.
-      const bool by_tag = ap->inter;  // workgroup-uniform
-      const uint64_t* grec = (const uint64_t*)&ap->inter_desc[mb];  // reference 1, this MB
+      const bool by_tag = vs.nrec != 0;  // workgroup-uniform
+      const uint64_t* grec = (const uint64_t*)&vs.inter_desc[mb];  // reference 1, this MB
       uint64_t rd0 = 0;
       if (early && tid == 0)
         rd0 = by_tag ? gran_ld(grec)
@@ -2201,7 +2289,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       bool ready0 = false;  // thread 0: the records were in before the search
       if (gstart && !early) {  // inter records of MBs bx..bx+3, and every cross-frame dependency they carry
         if (tid == 0) {
-          if (by_tag) rec_settle(*ap, grec, gran_ld(grec), by, mb);
+          if (by_tag) rec_settle(*ap, vs.epoch, grec, gran_ld(grec), by, mb);
           else wait_records(*ap, by, bx >> 2);
         }
         acquire_after_wait(ap->sys);  // the stale rows, references and previous output_cache
@@ -2220,15 +2308,15 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         if (bx == 0) {
           int lx[9], ly[9], n = 0;
           for (int r = max(by - 3, 0); r <= by - 1; r++)
-            for (int c = 0; c <= 2 && c < ap->wmb; c++) lx[n] = c, ly[n++] = r;
+            for (int c = 0; c <= 2 && c < vs.wmb; c++) lx[n] = c, ly[n++] = r;
           for (int k = tid; k < n * kGranulesPerMB; k += 256) {
             const int i = k / kGranulesPerMB, kk = k - i * kGranulesPerMB;
-            const uint64_t* gp = gran_at(*ap, lx[i], ly[i], kk);
-            win_put_k(L.win, oy, lx[i], ly[i], kk, gran_settle(*ap, gp, gran_ld(gp), by));
+            const uint64_t* gp = gran_at(vs.granules, vs.wmb, lx[i], ly[i], kk);
+            win_put_k(L.win, oy, lx[i], ly[i], kk, gran_settle(*ap, vs.epoch, gp, gran_ld(gp), by));
           }
         } else if (fresh_col) {
           win_put_k(L.win, oy, bx + 2, by - 1, tid,
-                    gran_settle(*ap, fresh_gp, fresh_g, by));
+                    gran_settle(*ap, vs.epoch, fresh_gp, fresh_g, by));
         }
       }
       acct_add(ap->acct, Acct::kCoderWindow, acct_now() - tacc);
@@ -2239,8 +2327,9 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       if (!kDecode) __builtin_amdgcn_s_waitcnt(kWaitVm0);
       acct_add(ap->acct, Acct::kCoderVm0, acct_now() - tv0);
       if (early && tid == 0) {
-        ready0 = by_tag ? (uint32_t)(rd0 >> 32) == ap->epoch : (int)rd0 >= ap->nref;
-        if (ready0) acquire_fence(ap->sys);  // completes during the search; waited for after it
+        const ViewGroup gv = view_block<ViewGroup>(ap);
+        ready0 = by_tag ? (uint32_t)(rd0 >> 32) == vs.epoch : (int)rd0 >= gv.nref;
+        if (ready0) acquire_fence(gv.sys);  // completes during the search; waited for after it
       }
       // source rows of this lane's group slot
       SrcRow s;  // biased u16 pairs (the encoder's source; unused when decoding)
@@ -2254,14 +2343,14 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         s.u[0] = m[128 + co] ^ 0x80008000u, s.u[1] = m[128 + co + 1] ^ 0x80008000u;
         s.v[0] = m[160 + co] ^ 0x80008000u, s.v[1] = m[160 + co + 1] ^ 0x80008000u;
       }
-      const bool pf3 = by >= 3 && bx + 3 < ap->wmb, pf2 = by >= 2 && bx + 3 < ap->wmb;
-      const bool pfs = by + 1 < ap->hmb && bx + 1 < ap->wmb;
+      const bool pf3 = by >= 3 && bx + 3 < vs.wmb, pf2 = by >= 2 && bx + 3 < vs.wmb;
+      const bool pfs = by + 1 < vs.hmb && bx + 1 < vs.wmb;
       uint64_t pg3 = 0, pg2 = 0;
       uint32_t pst = 0;
       if (tid < kGranulesPerMB) {
-        if (pf3) pg3 = gran_ld(gran_at(*ap, bx + 3, by - 3, tid));
-        if (pf2) pg2 = gran_ld(gran_at(*ap, bx + 3, by - 2, tid));
-        if (pfs && !early) pst = *(const uint32_t*)win_src(cs, ap->wa, bx, by + 1, tid);  // (early: after the wait)
+        if (pf3) pg3 = gran_ld(gran_at(vs.granules, vs.wmb, bx + 3, by - 3, tid));
+        if (pf2) pg2 = gran_ld(gran_at(vs.granules, vs.wmb, bx + 3, by - 2, tid));
+        if (pfs && !early) pst = *(const uint32_t*)win_src(view_block<ViewStale>(ap).stale, vs.wa, bx, by + 1, tid);  // (early: after the wait)
       }
 
       // ---- inter predictions, prefetched (the K1 records are final) ----
@@ -2274,13 +2363,14 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       BlockDesc ib;  // set by reference 1 (o == 0) before it is compared
       int ib_sad = 0;
       int ipa[2] = {0, 0}, ipb[2] = {0, 0};
-      auto load_inter = [&]() {  // the records (issue_records), then the predictions
+      // (s: the caller's block read of the view)
+      auto load_inter = [&](const ViewCoderStart& s) {  // the records (issue_records), then the predictions
 #pragma unroll
         for (int o = 0; o < kMaxRing - 1; o++) {
           if (o >= nref) break;
-          const uint64_t* r = (const uint64_t*)&ap->inter_desc[o * mbs + mb];
-          const BlockDesc rd = unpack_inter_desc((uint32_t)uni((int)rec_settle(*ap, r, rg[o][0], by, mb)));
-          const int rs = uni((int)rec_settle(*ap, r + 1, rg[o][1], by, mb));
+          const uint64_t* r = (const uint64_t*)&s.inter_desc[o * (s.wmb * s.hmb) + mb];
+          const BlockDesc rd = unpack_inter_desc((uint32_t)uni((int)rec_settle(*ap, s.epoch, r, rg[o][0], by, mb)));
+          const int rs = uni((int)rec_settle(*ap, s.epoch, r + 1, rg[o][1], by, mb));
           if (o == 0) {
             ib = rd, ib_sad = rs;
           } else {
@@ -2296,16 +2386,17 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         int dx = 0, dy = 0;
         if (sp) frac_dir(d.sp_index, &dx, &dy);
         _Pragma("unroll") for (int bi = 0; bi < 2; bi++) if (bi < nblk) {
-          ipa[bi] = pred_at(rp, ap->wa, (wave + 4 * bi) * 64 + lane, mx, my);
-          if (sp) ipb[bi] = pred_at(rp, ap->wa, (wave + 4 * bi) * 64 + lane, mx + dx, my + dy);
+          ipa[bi] = pred_at(rp, s.wa, (wave + 4 * bi) * 64 + lane, mx, my);
+          if (sp) ipb[bi] = pred_at(rp, s.wa, (wave + 4 * bi) * 64 + lane, mx + dx, my + dy);
         }
       };
       const uint64_t tr0 = acct_now();
-      if (!early) load_inter();
-      stamp(*ap, mb, 1);
+      if (!early) load_inter(vs);
+      stamp(ap->stamps, mb, 1);
       const uint64_t tr1 = acct_now();
+      ASM_MARK("mb_start end");
       __syncthreads();
-      stamp(*ap, mb, 2);
+      stamp(ap->stamps, mb, 2);
       tacc = acct_now();
       acct_add(ap->acct, Acct::kCoderRecords, tr1 - tr0);
       acct_add(ap->acct, Acct::kCoderPreBarrier, tacc - tr1);
@@ -2355,7 +2446,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
             const int st = second ? step >> 1 : step;
             if (second ? spec : grp < n0) {
               const int cx = bx0 - st + (k9 % 3) * st, cy = by0 + (second ? -st : jlo) + (k9 / 3) * st;
-              const bool ok = intra_valid(cx, cy, px, py, ap->wa, ap->ha);
+              const bool ok = intra_valid(cx, cy, px, py, vs.wa, vs.ha);
               int sad, mad;
               cand_row(L.win, oy, cx, ok ? cy : py - 48, gi, s, thr, sad, mad);
               if (gi == 0) {
@@ -2400,7 +2491,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
           const int q = (grp >> 2) & 1, nn = (grp & 3) | ((grp >> 3) << 2), c = 2 * nn + q;
           const int k9 = nn < 4 ? nn : nn + 1;  // skip the centre of the 3x3
           const int tx = bx0 + k9 % 3 - 1, ty = by0 + k9 / 3 - 1;
-          const bool ok = intra_valid(tx, ty, px, py, ap->wa, ap->ha);
+          const bool ok = intra_valid(tx, ty, px, py, vs.wa, vs.ha);
           int sad, mad;
           const uint64_t ts0 = acct_now();
           subpel_row(L.win, oy, bx0, ok ? by0 : py - 48, tx, ok ? ty : py - 48, uni(q), gi, s, thr, sad, mad);
@@ -2424,22 +2515,26 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         stamp(*ap, mb, 4);
         acct_add(ap->acct, Acct::kCoderSearch, acct_now() - tacc);
         if (early) {  // the group's records (and the cross-frame dependencies), then this MB's
+          // the block again, not kept live across the search
+          FA* aq = opaque_view(ap);
+          const ViewCoderStart ws = view_block<ViewCoderStart>(aq);
           tacc = acct_now();
           if (tid == 0) {
             if (!ready0) {
-              if (by_tag) rec_settle(*ap, grec, gran_ld(grec), by, mb);
-              else wait_records(*ap, by, bx >> 2);
-              acquire_fence(ap->sys);
+              const uint64_t* gr = (const uint64_t*)&ws.inter_desc[mb];
+              if (ws.nrec) rec_settle(*aq, ws.epoch, gr, gran_ld(gr), by, mb);
+              else wait_records(*aq, by, bx >> 2);
+              acquire_fence(aq->sys);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the acquire has completed
           }
           __syncthreads();
-          acct_add(ap->acct, Acct::kCoderGroupWait, acct_now() - tacc);
+          acct_add(aq->acct, Acct::kCoderGroupWait, acct_now() - tacc);
           tacc = acct_now();
-          if (tid < kGranulesPerMB && pfs) pst = *(const uint32_t*)win_src(cs, ap->wa, bx, by + 1, tid);
-          issue_records();
-          load_inter();
-          acct_add(ap->acct, Acct::kCoderInter, acct_now() - tacc);
+          if (tid < kGranulesPerMB && pfs) pst = *(const uint32_t*)win_src(view_block<ViewStale>(aq).stale, ws.wa, bx, by + 1, tid);
+          issue_records(ws);
+          load_inter(ws);
+          acct_add(aq->acct, Acct::kCoderInter, acct_now() - tacc);
         }
         d = make_desc(sel, px, py, thr, true, 0);
         int best_sad = sel.sad;
@@ -2478,6 +2573,10 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         }
       }
       ap = opaque_view(ap);  // after the searches: the view's fields re-read, not live across them
+      ASM_MARK("mb_publish begin");
+      const ViewCoderStart ps = view_block<ViewCoderStart>(ap);  // for the stores and the publish
+      const uint32_t tag = ps.epoch;
+      const int cw = ps.wa >> 1;
       stamp(*ap, mb, 5);
       const uint64_t tx5 = acct_now();
       // this lane's source elements for the residual, loaded after the
@@ -2543,10 +2642,10 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       if (tid < kGranulesPerMB) {
         if (pf3)
           win_put_k(L.win, oy, bx + 3, by - 3, tid,
-                    gran_settle(*ap, gran_at(*ap, bx + 3, by - 3, tid), pg3, by));
+                    gran_settle(*ap, ps.epoch, gran_at(ps.granules, ps.wmb, bx + 3, by - 3, tid), pg3, by));
         if (pf2)
           win_put_k(L.win, oy, bx + 3, by - 2, tid,
-                    gran_settle(*ap, gran_at(*ap, bx + 3, by - 2, tid), pg2, by));
+                    gran_settle(*ap, ps.epoch, gran_at(ps.granules, ps.wmb, bx + 3, by - 2, tid), pg2, by));
         if (pfs) win_put_k(L.win, oy, bx, by + 1, tid, pst);
       }
       if (!(type & kCopy)) {
@@ -2573,7 +2672,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
           } else {  // the decoded coefficients (the decoder's input_cache)
             int pl, ex, ey;
             elem_coords(e, px, py, pl, ex, ey);
-            qv = plane_of(planes(ap->coef), pl)[(size_t)ey * (pl ? cw : ap->wa) + ex];
+            qv = plane_of(planes(ap->coef), pl)[(size_t)ey * (pl ? cw : ps.wa) + ex];
           }
           // a block whose coefficients all quantized to zero inverse-transforms
           // to zero (transform.cpp:330-366, per-term truncations of 0): its
@@ -2597,7 +2696,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
             const int e = (wave + 4 * bi) * 64 + lane;
             int pl, ex, ey;
             elem_coords(e, px, py, pl, ex, ey);
-            cp[bi] = pick(planes(ap->coef_prev), pl)[(size_t)ey * (pl ? cw : ap->wa) + ex];
+            cp[bi] = pick(planes(ap->coef_prev), pl)[(size_t)ey * (pl ? cw : ps.wa) + ex];
           }
           _Pragma("unroll") for (int bi = 0; bi < 2; bi++) if (bi < nblk)
             coef_store_pair(*ap, (wave + 4 * bi) * 64 + lane, px, py, cp[bi]);
@@ -2620,7 +2719,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         if (!(lane & 1)) {
           const int r = lane >> 3, c2 = (lane & 7) >> 1;
           const int k = b < 4 ? (((b >> 1) * 8 + r) * 8 + (b & 1) * 4 + c2) : (128 + (b - 4) * 32 + r * 4 + c2);
-          gran_st(gran_at(*ap, bx, by, k),
+          gran_st(gran_at(ps.granules, ps.wmb, bx, by, k),
                   ((uint64_t)tag << 32) | ((uint32_t)pv[bi] & 0xFFFFu) | ((uint32_t)nb << 16));
         }
       }
@@ -2655,7 +2754,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       }
       __syncthreads();
       if (tid == 0)
-        gran_st(gran_at(*ap, bx, by, kGranulesPerMB),
+        gran_st(gran_at(ps.granules, ps.wmb, bx, by, kGranulesPerMB),
                 ((uint64_t)tag << 32) | ((d.block_type & kCopy) ? 0x100u : 0u) | d.q_index);
       stamp(*ap, mb, 9);
       if (CAIRO_ACCT) {
@@ -2668,6 +2767,8 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         acct_add(ap->acct, Acct::kCoderDrain, tx9 - tx8);
       }
       if (ap->stamps && tid == 0) ap->stamps[(size_t)mb * kStampPhases + 11] = __builtin_amdgcn_s_memtime();
+      more = bx + 1 < ps.wmb;
+      ASM_MARK("mb_publish end");
     }
   }
 }
@@ -3021,6 +3122,7 @@ FrameArgs make_frame_view(const EngineArgs& e, const FrameDesc& f, int j) {
   a.inject = e.inject;
   a.ng = (e.wmb + 3) >> 2;
   a.nref = a.inter ? e.ring - 1 : 1;
+  a.nrec = a.inter ? e.ring - 1 : 0;
   a.inter_done = e.sync + SyncLayout::inter_done(e.hmb, a.ng, j);
   a.progress = f.progress;
   a.prev_progress = f.prev_progress;

@@ -88,11 +88,19 @@ def main():
     # speculated stage was ever reused), and the share of macroblocks at each count
     coder["search_passes"] = {"per_mb": round(c["search_passes"] / mbs, 3)}
     coder["search_passes"].update({k: round(c["search_mbs_" + k] / mbs, 4) for k in ("2pass", "3pass", "4pass")})
+    # the prologue (inside "rest" and "records"): macroblock start to the fresh granule's load issued, per
+    # macroblock, and from there to the record loads issued, per macroblock that is not a group start (at a
+    # group start they go out after the search)
+    in_group = max(mbs - c["coder_tasks"] * ((w + 63) // 64), 1)
+    coder["prologue"] = {"to_fresh_load": round(us(c["coder_prologue_fresh"]) / mbs, 3),
+                         "to_record_loads_in_group": round(us(c["coder_prologue_records"]) / in_group, 3)}
     helper = {k: round(us(c["helper_" + k]) / groups, 3) for k in ("total", "wait", "deblock", "search", "catchup")}
     helper["rest"] = round(helper["total"] - sum(helper[k] for k in ("wait", "deblock", "search", "catchup")), 3)
     helper["dequeue_per_task"] = round(us(c["helper_dequeue"]) / max(c["helper_tasks"], 1), 2)
     helper["carry"] = round(us(c["helper_carry"]) / groups, 3)  # first load .. last store issued; inside "rest"
-    helper["deblock_phases"] = {k: round(us(c[k]) / groups, 3) for k in ("db_inputs", "db_filter", "db_write")}
+    # a searched inter task's entry to its first window DMA (inside "search"), per searched task
+    helper["group_start_per_searched_task"] = round(us(c["helper_group_start"]) / max(c["searched_tasks"], 1), 3)
+    helper["deblock_phases"] ={k: round(us(c[k]) / groups, 3) for k in ("db_inputs", "db_filter", "db_write")}
     helper["chunks_per_group"] = round(c["helper_chunks"] / groups, 3)
     mb = 1e6
     traffic = {k: round(c[k] / timed / mb, 2) for k in
