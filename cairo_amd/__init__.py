@@ -145,6 +145,8 @@ def lib() -> ctypes.CDLL:
         "cairo_ctx_set_outputs": (I, [P, I]),
         "cairo_ctx_fetch_coef": (I, [P, I, P]),
         "cairo_unserialize_slice": (I, [P, ctypes.POINTER(U), U, U, U, U, P, P, P, P]),
+        "cairo_table_check": (I, [P, U, U, U]),
+        "cairo_desc_check": (I, [P, P, U, U, U, U, P]),
         "cairo_stream_create": (I, [P, I, ctypes.POINTER(P)]),
         "cairo_stream_submit": (I, [P, P, I, U, U, U, ctypes.POINTER(I)]),
         "cairo_stream_collect": (I, [P, I, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -609,6 +611,19 @@ class Context:
         finally:
             self.release(t)
 
+    def decode_frame(self, table: np.ndarray, planes, index: int) -> np.ndarray:
+        """cairo_ctx_decode_frame: reconstruct frame `index` from a block table
+        and (y, u, v) coefficient planes -> RGB888.  The table must pass
+        table_check; one that does not is refused here, not decoded."""
+        if not table_check(table, self.wmb, self.hmb, self.ring):
+            raise CairoError("decode_frame: table_check refused the table", 3)
+        t = np.ascontiguousarray(table).view(np.uint8)
+        coef = np.concatenate([np.ascontiguousarray(p, dtype=np.int16).ravel() for p in planes])
+        assert coef.size == self.wa * self.ha * 3 // 2
+        rgb = np.empty((self.height, self.width, 3), np.uint8)
+        _ck(self.L.cairo_ctx_decode_frame(self.h, _ptr(t), _ptr(coef), index, _ptr(rgb)), "cairo_ctx_decode_frame")
+        return rgb
+
     def sync(self) -> None:
         _ck(self.L.cairo_ctx_sync(self.h), "cairo_ctx_sync")
 
@@ -879,6 +894,22 @@ def unserialize_slice(payload: bytes, nbits: int, wmb: int, hmb: int, ring: int,
     _ck(lib().cairo_unserialize_slice(_ptr(np.ascontiguousarray(buf)), ctypes.byref(rd), nbits, wmb, hmb, ring,
                                       _ptr(table), *(_ptr(p) for p in planes)), "cairo_unserialize_slice")
     return table, planes, rd.value - start
+
+
+def table_check(table: np.ndarray, wmb: int, hmb: int, ring: int) -> bool:
+    """cairo_table_check: may this block table go to the decode-mode engine?"""
+    t = np.ascontiguousarray(table).view(np.uint8)
+    assert t.size == wmb * hmb * 16
+    return bool(lib().cairo_table_check(_ptr(t), wmb, hmb, ring))
+
+
+def desc_check(descs: np.ndarray, mb_index, wmb: int, hmb: int, ring: int) -> np.ndarray:
+    """cairo_desc_check: is descs[k] legal as macroblock mb_index[k]? -> bool array."""
+    d = np.ascontiguousarray(descs, dtype=BLOCK_DESC).reshape(-1)
+    idx = np.ascontiguousarray(np.broadcast_to(np.asarray(mb_index, np.uint32), d.shape))
+    ok = np.zeros(d.size, np.uint8)
+    _ck(lib().cairo_desc_check(_ptr(d.view(np.uint8)), _ptr(idx), d.size, wmb, hmb, ring, _ptr(ok)), "cairo_desc_check")
+    return ok.astype(bool)
 
 
 def bits_append(dst: np.ndarray, pos: int, src: bytes, nbits: int) -> int:

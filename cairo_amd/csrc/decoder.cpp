@@ -4,9 +4,10 @@
 //
 // decode(): lazy init from the stream header, frame descriptor, host entropy
 // decode (unserialize_slice, into the persistent block table and coefficient
-// planes), then the GPU hot path (cairo_ctx_decode_frame: the decode-mode
-// engine reconstructs and deblocks the frame into its ring slot, and
-// convert_image writes RGB888), then the reference's frame-state update.
+// planes), the table's legality (cairo_table_check: a table the engine cannot
+// honour is an error), then the GPU hot path (cairo_ctx_decode_frame: the
+// decode-mode engine reconstructs and deblocks the frame into its ring slot,
+// and convert_image writes RGB888), then the reference's frame-state update.
 // Like the reference, decode consumes the caller's bit_stream and empties it.
 #include <cstdlib>
 #include <cstring>
@@ -23,21 +24,6 @@ int unserialize_slice(const uint8_t* data, uint32_t* read_index, uint32_t write_
 }
 
 namespace evx {
-
-namespace {
-
-// decode_block's switch (decode.cpp:14-142) accepts these seven types.
-inline bool legal_type(uint32 t) { return t <= 7 && t != 5; }
-
-// frac_index -> direction (motion.cpp:61-109); sp_index 0..7.
-inline void frac_dir(uint32 idx, int32 *dx, int32 *dy) {
-  static const int8_t kDx[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
-  static const int8_t kDy[8] = {-1, -1, -1, 0, 0, 1, 1, 1};
-  *dx = kDx[idx & 7];
-  *dy = kDy[idx & 7];
-}
-
-}  // namespace
 
 class gpu_decoder : public evx1_decoder {
  public:
@@ -69,8 +55,9 @@ class gpu_decoder : public evx1_decoder {
                                  ring_, table_, coef_, coef_ + ny, coef_ + ny + nc))
       return EVX_ERROR_EXECUTION_FAILURE;
     input->set_read_index(rd);
-    if (!valid_table()) return EVX_ERROR_EXECUTION_FAILURE;
     const uint8_t *tbl = reinterpret_cast<const uint8_t *>(table_);
+    // the engine trusts the table: a stream it cannot honour is an error
+    if (!cairo_table_check(tbl, wmb_, hmb_, ring_)) return EVX_ERROR_EXECUTION_FAILURE;
     if (fmt_ == CAIRO_FMT_RGB24 && !pitch_
             ? cairo_ctx_decode_frame(ctx_, tbl, coef_, f.index, static_cast<uint8_t *>(output))
             : cairo_ctx_decode_frame_fmt(ctx_, tbl, coef_, f.index, fmt_, pitch_, static_cast<uint8_t *>(output)))
@@ -130,39 +117,6 @@ class gpu_decoder : public evx1_decoder {
     frame_index_ = 0;
     initialized_ = true;
     return EVX_SUCCESS;
-  }
-
-  // The GPU reconstruction trusts the table; a corrupt stream must not send
-  // it outside the frame or the intra window.  Every stream the reference
-  // encoder writes passes: its candidates are in frame (motion.cpp:225-275)
-  // and the intra search reaches at most 32 px sideways and 48 px up / 16 px
-  // down, sub-pel neighbour included.  q_index and sp_index ranges are the
-  // quantizer's and the sub-pel direction table's.  (Any prediction target is
-  // safe: the slot is (index + R - target) mod R.)
-  bool valid_table() const {
-    const int32 xmax = (int32)wa_ - 16, ymax = (int32)ha_ - 16;
-    for (uint32 by = 0; by < hmb_; by++)
-      for (uint32 bx = 0; bx < wmb_; bx++) {
-        const cairo::BlockDesc &d = table_[by * wmb_ + bx];
-        const uint32 t = d.block_type & 0xFFu;
-        if (!legal_type(d.block_type)) return false;
-        if (!(t & cairo::kCopy) && d.q_index > 31) return false;
-        if (!(t & cairo::kMotion)) continue;
-        if (d.sp_pred > 1 || (d.sp_pred && (d.sp_index > 7 || d.sp_amount > 1))) return false;
-        const int32 px = (int32)bx * 16, py = (int32)by * 16;
-        int32 x0 = px + d.motion_x, y0 = py + d.motion_y, x1 = x0, y1 = y0;
-        if (d.sp_pred) {
-          int32 dx, dy;
-          frac_dir(d.sp_index, &dx, &dy);
-          x1 += dx, y1 += dy;
-        }
-        for (int k = 0; k < 2; k++) {
-          const int32 x = k ? x1 : x0, y = k ? y1 : y0;
-          if (x < 0 || x > xmax || y < 0 || y > ymax) return false;
-          if ((t & cairo::kIntra) && (x < px - 32 || x > px + 32 || y < py - 48 || y > py + 16)) return false;
-        }
-      }
-    return true;
   }
 
   bool initialized_ = false;

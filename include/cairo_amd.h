@@ -49,7 +49,11 @@ extern "C" {
  *      existing changes, so the version stays: detect them by their symbols.
  *   4  (unchanged) the scaled submit adds entry points only as well:
  *      cairo_source_size, cairo_scale_check, cairo_ctx_submit_scaled,
- *      cairo_stream_submit_scaled, cairo_kat_scale. */
+ *      cairo_stream_submit_scaled, cairo_kat_scale.
+ *   4  (unchanged) cairo_table_check and cairo_desc_check are added.  The
+ *      drop-in decoder refuses with an error some tables it used to decode
+ *      (see cairo_table_check); every stream the reference encoder writes
+ *      decodes as before. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -202,7 +206,8 @@ CAIRO_API int cairo_ctx_wait(cairo_ctx *ctx, int ticket, cairo_frame_result *out
  * (wmb*hmb 16-B descs) and coefficient planes (y | u | v contiguous, the
  * decoder's input_cache) into ring slot index % R, deblock it, and write it as
  * RGB888 (width*height*3, pitch 3*width) to host memory rgb.  Synchronous.
- * The descs must be valid (motion inside the frame; see decoder.cpp). */
+ * The engine trusts the descs: the caller checks them with cairo_table_check
+ * first (the drop-in decoder does), and must not pass a table it refuses. */
 CAIRO_API int cairo_ctx_decode_frame(cairo_ctx *ctx, const uint8_t *block_table, const int16_t *coef,
                                      uint32_t index, uint8_t *rgb);
 /* The same, written as a frame of format fmt with row pitch `pitch` (0: tight)
@@ -490,6 +495,30 @@ CAIRO_API int cairo_precode_slice(const uint8_t *block_table, uint32_t wmb, uint
 CAIRO_API int cairo_unserialize_slice(const uint8_t *data, uint32_t *read_index, uint32_t write_index,
                                       uint32_t wmb, uint32_t hmb, uint32_t ring, uint8_t *block_table,
                                       int16_t *coef_y, int16_t *coef_u, int16_t *coef_v);
+
+/* ---- legality of a decoded block table (host only, no device) -------------
+ * 1 when the decode-mode engine reconstructs every desc of the table (wmb*hmb
+ * 16-B descs) as the reference decoder does, else 0.  Every table the
+ * reference encoder can write passes.  Per macroblock at (px, py):
+ *   - block_type in {0, 1, 2, 3, 4, 6, 7} (decode.cpp:14-142);
+ *   - without the copy bit: 1 <= q_index <= 31 (quantize.cpp:65-68);
+ *   - without the intra bit: 1 <= prediction_target <= ring-1
+ *     (encode.cpp:17-67);
+ *   - with the motion bit: sp_pred <= 1, and when set sp_amount <= 1 and
+ *     sp_index <= 7; the block at the vector and, when sp_pred, at its sub-pel
+ *     neighbour (motion.cpp:61-109) lies inside the wmb*16 x hmb*16 frame;
+ *   - intra with motion: both points (x, y) also lie in [px-32, px+32] x
+ *     [py-48, py+16] and outside the region not yet coded,
+ *     !(y > py-16 && x > px-16) (motion.cpp:238-241, 303-306).
+ * A stream of ring size 3 that used target 2 arrives with target 0 (one target
+ * bit, serialize.cpp:179) and is refused. */
+CAIRO_API int cairo_table_check(const uint8_t *block_table, uint32_t wmb, uint32_t hmb, uint32_t ring);
+/* The same rules desc by desc: ok[k] = 1 when descs[k] is legal as macroblock
+ * mb_index[k] (raster index) of such a frame, else 0; a table is legal when
+ * each of its descs is legal at its own index.  Returns 0, or
+ * EVX_ERROR_INVALIDARG (1). */
+CAIRO_API int cairo_desc_check(const uint8_t *descs, const uint32_t *mb_index, uint32_t n, uint32_t wmb,
+                               uint32_t hmb, uint32_t ring, uint8_t *ok);
 
 /* ---- frame pipeline ---------------------------------
  * GPU hot path + host entropy for a stream of frames: the caller submits

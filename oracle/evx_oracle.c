@@ -1158,25 +1158,31 @@ static void append_bytes(obits *o, const uint8_t *b, uint32_t n) {
         for (int s = 0; s < 8; s++) put_bit(o, (b[k] >> s) & 1u);
 }
 
+/* Size the state for a frame (initialize_context, common.cpp:79-150). */
+static int state_init(orc_encoder *e, int width, int height) {
+    e->width = (uint16_t)width;
+    e->height = (uint16_t)height;
+    e->wa = (width + 15) & ~15;
+    e->ha = (height + 15) & ~15;
+    e->wmb = e->wa / 16;
+    e->hmb = e->ha / 16;
+    int ok = planes_alloc(&e->input, e->wa, e->ha) && planes_alloc(&e->output, e->wa, e->ha) &&
+             planes_alloc(&e->predeblock, e->wa, e->ha);
+    e->slots = (planes *)calloc((size_t)e->ring, sizeof(planes));
+    for (int k = 0; k < e->ring && ok; k++) ok = planes_alloc(&e->slots[k], e->wa, e->ha);
+    e->table = (uint8_t *)calloc((size_t)e->wmb * e->hmb, 16);
+    e->inter_descs = (uint8_t *)calloc((size_t)(e->ring > 1 ? e->ring - 1 : 1) * e->wmb * e->hmb, 16);
+    e->inter_sads = (int32_t *)calloc((size_t)(e->ring > 1 ? e->ring - 1 : 1) * e->wmb * e->hmb, 4);
+    if (!ok || !e->table || !e->inter_descs || !e->inter_sads) return 10;
+    e->initialized = 1;
+    return 0;
+}
+
 int orc_encode(orc_encoder *e, const uint8_t *rgb, int width, int height, uint8_t *out,
                uint32_t cap_bytes, uint32_t *bit_pos) {
     obits o = {out, cap_bytes * 8u, *bit_pos, 0};
-    if (!e->initialized) { /* evx1enc.cpp:66-90, common.cpp:79-150 */
-        e->width = (uint16_t)width;
-        e->height = (uint16_t)height;
-        e->wa = (width + 15) & ~15;
-        e->ha = (height + 15) & ~15;
-        e->wmb = e->wa / 16;
-        e->hmb = e->ha / 16;
-        int ok = planes_alloc(&e->input, e->wa, e->ha) && planes_alloc(&e->output, e->wa, e->ha) &&
-                 planes_alloc(&e->predeblock, e->wa, e->ha);
-        e->slots = (planes *)calloc((size_t)e->ring, sizeof(planes));
-        for (int k = 0; k < e->ring && ok; k++) ok = planes_alloc(&e->slots[k], e->wa, e->ha);
-        e->table = (uint8_t *)calloc((size_t)e->wmb * e->hmb, 16);
-        e->inter_descs = (uint8_t *)calloc((size_t)(e->ring > 1 ? e->ring - 1 : 1) * e->wmb * e->hmb, 16);
-        e->inter_sads = (int32_t *)calloc((size_t)(e->ring > 1 ? e->ring - 1 : 1) * e->wmb * e->hmb, 4);
-        if (!ok || !e->table || !e->inter_descs || !e->inter_sads) return 10;
-        e->initialized = 1;
+    if (!e->initialized) { /* evx1enc.cpp:66-90 */
+        if (state_init(e, width, height)) return 10;
         /* evx_header (common.h:50-62, pack(2)); byte 7 is an unwritten pad in
          * the reference, written as 0 here. */
         uint8_t h[14] = {'E', 'V', 'X', '1', 14, 0, (uint8_t)e->ring, 0, 47, 2,
@@ -1207,6 +1213,35 @@ int orc_encode(orc_encoder *e, const uint8_t *rgb, int width, int height, uint8_
     if (o.err) return 10;
     e->type = 1; /* evx1enc.cpp:138-153 */
     if (((e->index + 1) % PERIODIC_INTRA) == 0) e->type = 0;
+    e->index++;
+    return 0;
+}
+
+/* The decoder's frame engine (engine_decode_frame, decode.cpp:172-198, after
+ * its unserialize_slice): decode_slice's raster loop (decode.cpp:146-170) over
+ * the given block table (wmb*hmb descs) and coefficient planes (the decoder's
+ * input_cache) into ring slot index % R, a snapshot of the planes before the
+ * deblock, deblock_image_filter (decode.cpp:187) with the same table, and the
+ * frame-state update (evx1dec.cpp:119-120).  The planes start from zero
+ * (planes_alloc, as image::allocate does, image.cpp:70-94), which is what an intra
+ * vector of frame 0 or a target beyond the frames decoded so far reads. */
+int orc_decode_frame(orc_encoder *e, int width, int height, const uint8_t *table, const int16_t *coef_y,
+                     const int16_t *coef_u, const int16_t *coef_v) {
+    if (!e->initialized && state_init(e, width, height)) return 10;
+    if (width != e->width || height != e->height) return 8;
+    planes coef = {(int16_t *)coef_y, (int16_t *)coef_u, (int16_t *)coef_v, e->wa, e->ha};
+    planes *cur = &e->slots[slot_of(e, 0)];
+    uint32_t bi = 0;
+    memcpy(e->table, table, (size_t)e->wmb * e->hmb * 16);
+    for (int j = 0; j < e->ha; j += 16) /* decode_slice, decode.cpp:155-167 */
+        for (int i = 0; i < e->wa; i += 16) {
+            const bdesc *d = tbl(e->table, bi++);
+            decode_block(e, d, mb_at(&coef, i, j), i, j, mb_at(cur, i, j));
+        }
+    memcpy(e->predeblock.y, cur->y, (size_t)e->wa * e->ha * 2);
+    memcpy(e->predeblock.u, cur->u, (size_t)e->wa * e->ha / 2);
+    memcpy(e->predeblock.v, cur->v, (size_t)e->wa * e->ha / 2);
+    orc_deblock(e->table, cur->y, cur->u, cur->v, e->wa, e->ha);
     e->index++;
     return 0;
 }

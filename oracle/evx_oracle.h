@@ -41,6 +41,15 @@ void orc_set_quality(orc_encoder *enc, int quality);
 int orc_encode(orc_encoder *enc, const uint8_t *rgb, int width, int height,
                uint8_t *out, uint32_t out_capacity_bytes, uint32_t *bit_pos);
 
+/* The decoder's frame engine after the entropy decode (decode_slice and the
+ * deblock of engine_decode_frame, decode.cpp:146-190): frame `index` (counted
+ * from 0 by this call) from a block table (16 B per MB) and the coefficient
+ * planes, into ring slot index % R.  Sizes the state on first use, like
+ * orc_encode; orc_plane / orc_predeblock_plane then show the result.  Use a
+ * handle either for encoding or for decoding. */
+int orc_decode_frame(orc_encoder *enc, int width, int height, const uint8_t *table,
+                     const int16_t *coef_y, const int16_t *coef_u, const int16_t *coef_v);
+
 /* Introspection for parity tests.  which: 0 = input_cache, 1 = output_cache,
  * 2 + k = ring slot k.  plane: 0 Y, 1 U, 2 V.  Pitch = plane width. */
 const int16_t *orc_plane(const orc_encoder *enc, int which, int plane);

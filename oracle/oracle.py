@@ -41,6 +41,8 @@ def lib() -> ctypes.CDLL:
         L.orc_set_quality.argtypes = [P, I]
         L.orc_encode.restype = I
         L.orc_encode.argtypes = [P, P, I, I, P, U, ctypes.POINTER(U)]
+        L.orc_decode_frame.restype = I
+        L.orc_decode_frame.argtypes = [P, I, I, P, P, P, P]
         for n in ("orc_plane",):
             getattr(L, n).restype = P
             getattr(L, n).argtypes = [P, I, I]
@@ -183,6 +185,26 @@ class OracleEncoder:
         d = np.frombuffer(ctypes.string_at(self.L.orc_inter_descs(self.h), n * 16), BLOCK_DESC).copy()
         s = np.frombuffer(ctypes.string_at(self.L.orc_inter_sads(self.h), n * 4), np.int32).copy()
         return d, s
+
+
+class OracleDecoder(OracleEncoder):
+    """The reference decoder's frame engine after its entropy decode
+    (orc_decode_frame): decode(table, planes) reconstructs and deblocks the
+    next frame; planes(2 + k), predeblock() and dims() then read it."""
+
+    def __init__(self, width: int, height: int, ring: int = 4):
+        super().__init__(ring)
+        self.width, self.height = width, height
+
+    def decode(self, table: np.ndarray, planes) -> None:
+        t = np.ascontiguousarray(table).view(np.uint8)
+        wa, ha = (self.width + 15) & ~15, (self.height + 15) & ~15
+        assert t.size == (wa // 16) * (ha // 16) * 16
+        y, u, v = (np.ascontiguousarray(a, dtype=np.int16) for a in planes)
+        assert y.shape == (ha, wa) and u.shape == v.shape == (ha // 2, wa // 2)
+        st = self.L.orc_decode_frame(self.h, self.width, self.height, _ptr(t), _ptr(y), _ptr(u), _ptr(v))
+        if st:
+            raise RuntimeError(f"oracle decode failed: {st}")
 
 
 def abac_feed(words: np.ndarray, nbits: int) -> tuple[bytes, int]:

@@ -35,7 +35,12 @@ def test_entropy_random_tables(orc, cairo):
     The oracle's entropy path is reached through a hand-built encoder state:
     we compare the product with itself across two independent layouts and
     with the oracle on natural data above; here we check determinism and the
-    exp-Golomb length law."""
+    exp-Golomb length law.  The host decode then has to recover them: every
+    field the stream carries and every coefficient (copy macroblocks carrying
+    zeros, as a first frame's do); tests/test_tables.py does the same over the
+    generator's sequences."""
+    from tests.test_tables import carried, check_stream_fields
+
     rng = np.random.default_rng(7)
     wmb, hmb = 6, 4
     table = np.zeros(wmb * hmb, cairo.BLOCK_DESC)
@@ -54,6 +59,13 @@ def test_entropy_random_tables(orc, cairo):
     a = cairo.serialize_slice(table, wmb, hmb, 4, y, u, v)
     b = cairo.serialize_slice(table.copy(), wmb, hmb, 4, y.copy(), u.copy(), v.copy())
     assert a == b and a[1] > 0
+    want = carried(table, (y, u, v), None, wmb, hmb)
+    pay, nb = cairo.serialize_slice(table, wmb, hmb, 4, *want)
+    got, planes, used = cairo.unserialize_slice(pay, nb, wmb, hmb, 4)
+    assert used == nb
+    check_stream_fields(got, table, 4)
+    for p, q in zip(planes, want):
+        np.testing.assert_array_equal(p, q)
 
 
 def _bits(buf: bytes, n: int):

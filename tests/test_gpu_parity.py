@@ -456,7 +456,9 @@ def _append_record(st, out, pos, t, tk, ref, w, h, ring, q):
 # converted to RGB.
 # ---------------------------------------------------------------------------
 
-def _decode_round_trip(orc, cairo, w, h, ring, q, frames, intra_every=0):
+def _decode_round_trip(orc, cairo, w, h, ring, q, frames, intra_every=0, make=None):
+    """make(w, h, t) -> RGB frame t (band4 when None)."""
+    make = make or orc.make_frame
     e = orc.OracleEncoder(ring)
     e.set_quality(q)
     enc = cairo.Encoder(ring=ring)
@@ -467,7 +469,7 @@ def _decode_round_trip(orc, cairo, w, h, ring, q, frames, intra_every=0):
         if intra_every and t % intra_every == 0:
             e.insert_intra()
             enc.insert_intra()
-        rgb = orc.make_frame(w, h, t)
+        rgb = make(w, h, t)
         e.encode(rgb)
         bs.empty()
         enc.encode(rgb, bs)
@@ -490,6 +492,17 @@ def test_decoder_intra_and_ragged(orc, cairo):
     # are written with log2(R) = 1 bit, serialize.cpp:179, so target 2 reads as 0)
     _decode_round_trip(orc, cairo, 200, 120, 2, 16, 6)
     _decode_round_trip(orc, cairo, 64, 48, 4, 16, 5)
+
+
+@pytest.mark.parametrize("ring", [2, 4])
+@pytest.mark.parametrize("kind", ["noise", "ties", "gradient", "pan"])
+def test_decoder_content(orc, cairo, kind, ring):
+    """Streams of content the search treats unlike band4: full searches
+    (noise), order-dependent ties, sub-pel winners (gradient), vectors at the
+    search's reach and a scene cut (pan)."""
+    from tests import content
+
+    _decode_round_trip(orc, cairo, 352, 288, ring, 16, 5, make=lambda w, h, t: content.make(kind, w, h, t))
 
 
 def test_decoder_720p(orc, cairo):
