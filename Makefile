@@ -62,6 +62,7 @@ check-knobs:
 	@mkdir -p $(KNOB_OBJ)
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_ACCT=1 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/acct.o
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_ACCT=1 -DCAIRO_CODER_CARRY=1 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/acct_coder_carry.o
+	$(HIPCC) $(HIPFLAGS) -DCAIRO_ACCT=1 -DCAIRO_ACCT_START=0 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/acct_no_start.o
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_TOOLS_BUILD -DCAIRO_ATTR_SKIP=1 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/attr1.o
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_TOOLS_BUILD -DCAIRO_ATTR_SKIP=4 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/attr4.o
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_TOOLS_BUILD -DCAIRO_ATTR_SKIP=120 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/attr120.o

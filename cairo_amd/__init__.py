@@ -507,7 +507,10 @@ class Context:
                    "search_passes", "search_mbs_2pass", "search_mbs_3pass", "search_mbs_4pass",
                    "coder_xform_copy", "coder_copy_mbs", "coder_xform_coded", "coder_coded_mbs",
                    "helper_carry", "carry_bytes",
-                   "coder_prologue_fresh", "coder_prologue_records", "helper_group_start")
+                   "coder_prologue_fresh", "coder_prologue_records", "helper_group_start",
+                   "start_older_searched", "start_ref1_searched", "start_older_idle", "start_ref1_idle",
+                   "older_searched", "older_idle", "ref1_idle",
+                   "flag_set", "fallback_polls", "fallback_full", "lvl2_runs", "idle_groups", "idle_group_time")
 
     def read_acct(self, reset: bool = False) -> dict:
         """Engine time accounting (set_debug(32) on a CAIRO_ACCT=1 build): 10 ns

@@ -113,7 +113,7 @@ enum TimeoutKind : int32_t {
 #ifndef CAIRO_ACCT
 #define CAIRO_ACCT 0
 #endif
-constexpr int kAcctShards = 64, kAcctWords = 53;
+constexpr int kAcctShards = 64, kAcctWords = 66;
 struct Acct {
   // row coders
   static constexpr int kCoderTasks = 0, kCoderTotal = 1, kCoderGroupWait = 2, kCoderWindow = 3, kCoderSearch = 4,
@@ -159,6 +159,20 @@ struct Acct {
   // (inside a group; at a group start they go out after the search), and a
   // searched inter task's entry to its first window DMA
   static constexpr int kCoderProFresh = 50, kCoderProRecords = 51, kHelperGroupStart = 52;
+  // the helper's group start, per inter task: its entry to the
+  // first window DMA of a searched task, or to the record stores of one that
+  // searches nothing, by reference (older: offsets >= 2); the counts of the
+  // tasks behind those sums (reference 1's searched ones are kSearchedTasks -
+  // kOlderSearched)
+  static constexpr int kStartOlderSearched = 53, kStartRef1Searched = 54, kStartOlderIdle = 55, kStartRef1Idle = 56,
+                       kOlderSearched = 57, kOlderIdle = 58, kRef1Idle = 59;
+  // of the tasks that needed "is the whole window final" (every reference-1
+  // task, every searched older one): the wait's flag was set / it was clear
+  // and thread 0 polled; the polls that found full; the level-2 stagings run
+  static constexpr int kFlagSet = 60, kFallbackPolls = 61, kFallbackFull = 62, kLvl2Runs = 63;
+  // inter groups none of whose tasks searched, and their time from the
+  // group's start to reference 1's records
+  static constexpr int kIdleGroups = 64, kIdleGroupTime = 65;
 };
 
 // Frames per engine launch.

@@ -186,6 +186,16 @@ __device__ __forceinline__ void acct_add(uint64_t* acct, int k, uint64_t v) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The group-start counters (kernels.h Acct 53 ff.) cost a dozen
+// atomics per inter task; -DCAIRO_ACCT_START=0 leaves them out of an
+// accounting build whose totals are to be compared with an older one's.
+#ifndef CAIRO_ACCT_START
+#define CAIRO_ACCT_START CAIRO_ACCT
+#endif
+__device__ __forceinline__ void acct_start(uint64_t* acct, int k, uint64_t v) {
+  if (CAIRO_ACCT_START) acct_add(acct, k, v);
+}
+
 // Assembly comments that bracket a stretch of a kernel for tools/smem_counts.py
 // (-DCAIRO_ASM_MARKS=1 builds; a product build emits nothing).
 #ifndef CAIRO_ASM_MARKS
@@ -978,14 +988,28 @@ __device__ __forceinline__ bool deblock_chunk_ready(FA& a, int r, const DbState&
 __device__ __forceinline__ void deblock_chunk(FA& a, int r, DbLds& D, DbState& st, bool known_ready = false);
 __device__ __forceinline__ bool deblock_pending(FA& a, const DbState& st);
 
+// Need of the group's level-1 / level-2 windows: (MB row whose deblock
+// progress counts, luma columns).
+__device__ __forceinline__ int inter_need_cols(FA& a, int g, int level) {
+  return min(64 * g + (level == 1 ? 80 : 96), a.wa);
+}
+
 // Helper wait (whole workgroup): until the deblock progress of frame
 // index-back (back = 1: the previous frame, 2: the one before) of MB row rr
 // reaches need, running this row's ready deblock chunks meanwhile (kDeblock);
 // then acquire what the progress word released.  Bounded like every wait (the
 // error word ends it).
+// want_full (full2 is a word in LDS): the poll that satisfies
+// the wait also loads the level-2 words of group g (rows r+3 and r+2, clamped) beside
+// the word it tests, and *full2 says whether both have reached level 2's
+// columns: the group's window is final as a whole.  Progress words only
+// grow, so a "full" seen here stays true; the acquire at the wait's exit
+// follows these loads too.  Written before the exit's barrier, so it is
+// workgroup-uniform after the wait; 0 when the wait gave up.
 template <bool kDeblock = true>
 __device__ __forceinline__ void helper_wait(FA& a, int back, int r, int rr, int need, DbLds& D, DbState& st,
-                                            int* flag) {
+                                            int* flag, int* full2 = nullptr, bool want_full = false,
+                                            int g = 0) {
   volatile int* vflag = flag;
   const uint64_t* pp = back == 1 ? a.prev_progress : a.prev2_progress;
   uint64_t t0 = 0;
@@ -994,14 +1018,25 @@ __device__ __forceinline__ void helper_wait(FA& a, int back, int r, int rr, int 
   for (;;) {
     int d = 0;
     if (threadIdx.x == 0) {
-      // the progress poll and the deblock readiness loads in flight together
+      // the progress poll, the level-2 words and the deblock readiness loads
+      // in flight together
       const uint64_t pv = pp ? progress_peer(a.sys, pp + rr) : ~0ull;
+      uint64_t w3 = ~0ull, w2 = ~0ull;
+      if (want_full && pp) {
+        w3 = progress_peer(a.sys, pp + min(r + 3, a.hmb - 1));
+        w2 = progress_peer(a.sys, pp + min(r + 2, a.hmb - 1));
+      }
       const bool dbr = kDeblock && deblock_pending(a, st) && deblock_chunk_ready(a, r, st);
       if (a.inject && r == min(1, a.hmb - 1)) {  // test hook: this wait "times out" at once
         report_timeout(a, kWaitInjected, r, need, rr | (back << 16), pv);
         d = 1;
+        if (want_full) *full2 = 0;
       } else if (pv >= tagged(a.epoch - back, need)) {
         d = 1;
+        if (want_full) {
+          const uint64_t want = tagged(a.epoch - back, inter_need_cols(a, g, 2));
+          *full2 = (w3 >= want) & (w2 >= want);
+        }
       } else if (dbr) {
         d = 2;
       } else {  // nothing to do: back off
@@ -1014,6 +1049,7 @@ __device__ __forceinline__ void helper_wait(FA& a, int back, int r, int rr, int 
           report_timeout(a, kWaitPrevProgress, r, need, rr | (back << 16), pv);
           d = 1;
         }
+        if (d && want_full) *full2 = 0;
       }
     }
     d = wg_broadcast(vflag, d);
@@ -1042,6 +1078,13 @@ struct InterLds {
   // references, computed together at the group start
   alignas(16) int16_t src[4][384];
   int zsad[kMaxRing][4], zmad[kMaxRing][4];
+  // whether wave w's macroblock needs a search in reference off (the older
+  // references; left by zero_mv_older behind a barrier)
+  int zneed[kMaxRing][4];
+  // helper_wait's "the whole window is final" of the group: [0] from the
+  // wait for the previous frame, [1] from the wait for the one before (two
+  // words: the next wait may write one while a wave still reads the other)
+  int wfull[2];
 };
 
 // Wave w's source macroblock (4g + w, r) into L.src[w], row-major: luma
@@ -1104,30 +1147,36 @@ __device__ __forceinline__ SrcRow src_rows_lds(const InterLds& L, int wave, int 
 
 // The zero-MV SAD / MAD of references 2..nref for the group (all loads of a
 // wave issued together), into L.zsad / L.zmad.  After the wait for frame
-// index-2's level-1 window (which covers the zero-MV block).
+// index-2's level-1 window (which covers the zero-MV block).  Also leaves
+// whether each wave's macroblock needs a search in each of them (L.zneed:
+// inter_task's test, 0 for a wave past the row's end), and ends in a
+// workgroup barrier, so the older tasks read every wave's without one.
 __device__ __forceinline__ void zero_mv_older(FA& a, int r, int g, InterLds& L) {
   const int wave = threadIdx.x >> 6, x = 4 * g + wave;
   acct_add(a.acct, Acct::kZeroMvBytes, 768ull * (a.nref - 1) * (uint64_t)min(4, a.wmb - 4 * g));
-  if (x >= a.wmb) return;
-  const int px = x * kMB, py = r * kMB;
-  const Px6 src = src_px_lds(L, wave);
-  Px6 ref[kMaxRing - 1];
+  if (x < a.wmb) {
+    const int px = x * kMB, py = r * kMB;
+    const int thr = (a.quality >> 2) + 1;
+    const Px6 src = src_px_lds(L, wave);
+    Px6 ref[kMaxRing - 1];
 #pragma unroll
-  for (int off = 2; off < kMaxRing; off++)
-    if (off <= a.nref) ref[off - 1] = px_from_planes(RECON_AT(a, off), a.wa, px, py);
+    for (int off = 2; off < kMaxRing; off++)
+      if (off <= a.nref) ref[off - 1] = px_from_planes(RECON_AT(a, off), a.wa, px, py);
 #pragma unroll
-  for (int off = 2; off < kMaxRing; off++) {
-    if (off > a.nref) break;
-    int sad, mad;
-    sad_mad(src, ref[off - 1], sad, mad);
-    if ((threadIdx.x & 63) == 0) L.zsad[off][wave] = sad, L.zmad[off][wave] = mad;
+    for (int off = 2; off < kMaxRing; off++) {
+      if (off > a.nref) break;
+      int sad, mad;
+      sad_mad(src, ref[off - 1], sad, mad);
+      if ((threadIdx.x & 63) == 0) {
+        L.zsad[off][wave] = sad, L.zmad[off][wave] = mad;
+        L.zneed[off][wave] = mad >= thr && !(CAIRO_ATTR_SKIP & 8);
+      }
+    }
+  } else if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int off = 2; off < kMaxRing; off++) L.zneed[off][wave] = 0;
   }
-}
-
-// Need of the group's level-1 / level-2 windows: (MB row whose deblock
-// progress counts, luma columns).
-__device__ __forceinline__ int inter_need_cols(FA& a, int g, int level) {
-  return min(64 * g + (level == 1 ? 80 : 96), a.wa);
+  __syncthreads();
 }
 
 // Build switch (accounting and A/B builds): 1 keeps the output_cache carry of
@@ -1140,6 +1189,8 @@ __device__ __forceinline__ int inter_need_cols(FA& a, int g, int level) {
 // scope; sc0 sc1: the system-scope form, for a view shared across devices).
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) u32x4 gbl_u32x4;
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_u __attribute__((aligned(2)));  // four int16 of a plane row, at any even address
 __device__ __forceinline__ void store16_through(bool sys, int16_t* p, u32x4 v) {
   if (sys)
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
@@ -1173,36 +1224,54 @@ __device__ __forceinline__ void store16_through(bool sys, int16_t* p, u32x4 v) {
 // frame sees the carried values through: this acknowledged carry -> the
 // records -> the coder's acquire -> its info granule -> the deblock ->
 // the progress word -> the next frame's helper_wait.
-// Returns whether anything was stored (workgroup-uniform): not when coef and
-// coef_prev are the same planes (one staging slot).
-__device__ __forceinline__ bool carry_group(FA& a, int r, int g) {
-  if (CAIRO_CODER_CARRY) return false;
-  const PlaneSet dst = planes(a.coef), src = planes(a.coef_prev);
-  if (dst.y == src.y) return false;
-  const uint64_t t0 = acct_now();
+//
+// The load and the store are two calls: inter_task issues the
+// load beside reference 1's zero-MV loads and its level-2 poll, one round
+// trip for the three, and stores as soon as the carry's data is there.
+// carry_wanted: whether the group is carried at all (workgroup-uniform): not
+// when coef and coef_prev are the same planes (one staging slot).
+__device__ __forceinline__ bool carry_wanted(FA& a) {
+  return !CAIRO_CODER_CARRY && planes(a.coef).y != planes(a.coef_prev).y;
+}
+// This lane's chunk: its element offset in its plane (pl), or -1 for a lane
+// that carries nothing.
+__device__ __forceinline__ ptrdiff_t carry_chunk(FA& a, int r, int g, int& pl) {
   const int t = threadIdx.x;
-  int pl, row, x, col;  // plane, plane row, macroblock column, first plane column of this lane's chunk
+  int row, x, col;  // plane row, macroblock column, first plane column of this lane's chunk
   if (t < 128) {
     pl = 0, row = r * kMB + (t >> 3), x = 4 * g + ((t & 7) >> 1), col = 4 * g * kMB + 8 * (t & 7);
   } else {
     const int k = t - 128;
     pl = 1 + (k >> 5), row = r * (kMB / 2) + ((k & 31) >> 2), x = 4 * g + (k & 3), col = x * (kMB / 2);
   }
-  if (t < 192 && x < a.wmb) {
-    const size_t off = (size_t)row * (pl ? a.wa >> 1 : a.wa) + col;
-    const u32x4 v = *(const gbl_u32x4*)(pick(src, pl) + off);
-    store16_through(a.sys, pick(dst, pl) + off, v);
-  }
-  acct_add(a.acct, Acct::kHelperCarry, acct_now() - t0);
-  acct_add(a.acct, Acct::kCarryBytes, 768ull * (uint64_t)min(4, a.wmb - 4 * g));
-  return true;
+  if (t >= 192 || x >= a.wmb) return -1;
+  return (ptrdiff_t)((size_t)row * (pl ? a.wa >> 1 : a.wa) + col);
+}
+__device__ __forceinline__ u32x4 carry_load(FA& a, int pl, ptrdiff_t off) {
+  return *(const gbl_u32x4*)(pick(planes(a.coef_prev), pl) + off);
+}
+__device__ __forceinline__ void carry_store(FA& a, int pl, ptrdiff_t off, u32x4 v) {
+  store16_through(a.sys, pick(planes(a.coef), pl) + off, v);
 }
 
 // Reference offset `off` of group g of row r: the tagged records of the
 // group's macroblocks are stored and left in flight (the coder polls them).
-// carried: carry_group stored this group's coefficients (off == 1 only); they
-// are acknowledged before the records are stored.
-__device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterLds& L, DbLds& D, DbState& st,
+// kRef1: off == 1, the previous frame, after helper_wait(1); else an older
+// reference, after helper_wait(2) and zero_mv_older.
+// carried (kRef1 only, workgroup-uniform): the group's output_cache carry is
+// done here (carry_wanted); its stores are acknowledged before the records
+// are stored.
+// The group start.  L.wfull[kRef1 ? 0 : 1] is the wait's "the
+// whole window is final"; set, it is used as it is (progress words only grow,
+// and the wait's exit acquired what those words released), clear, thread 0
+// polls the two level-2 words once.  An older task knows every wave's need
+// from zero_mv_older: when no wave searches it issues no load and meets no
+// barrier, and with the wait's flag set it goes to its window DMA without a
+// barrier either.  Reference 1 issues the carry's load, the zero-MV loads and
+// that poll before it waits for any of them.
+// Returns whether any wave searched (workgroup-uniform).
+template <bool kRef1>
+__device__ __forceinline__ bool inter_task(FA& a0, int r, int g, int off, InterLds& L, DbLds& D, DbState& st,
                                            int* flag, uint64_t* is, bool carried = false) {
   FA& a = *opaque_view(&a0);
   ASM_MARK("group_start begin");
@@ -1223,44 +1292,113 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
   s.sad = s.mad = 0;
   SrcRow srow;  // biased source rows of this lane's group slot (integer steps)
   const int ox = 4 * g * kMB - 32, oy = py - 32;  // window origin
-  if (valid) {  // the source from the group's LDS copy
-    src = src_px_lds(L, wave);
-    srow = src_rows_lds(L, wave, threadIdx.x & 15);
-    if (off >= 2) {  // zero-MV computed at the group start
-      s.sad = L.zsad[off][wave], s.mad = L.zmad[off][wave];
-    } else {  // zero-MV candidate straight from the planes
-      sad_mad(src, px_from_planes(ref, a.wa, px, py), s.sad, s.mad);
+  // Is the reference already final over the whole window (level 2 too)?
+  // Always, in practice, for the older references (frame index-2 runs far
+  // ahead): then the window is staged in one go and the steps skip the
+  // per-step level-2 decisions and their barriers.
+  const uint64_t* pp = kRef1 ? a.prev_progress : a.prev2_progress;
+  const uint64_t want = tagged(a.epoch - (kRef1 ? 1 : 2), inter_need_cols(a, g, 2));
+  // the wait's flag: from LDS behind the wait's barrier, workgroup-uniform
+  const bool wf = uni(L.wfull[kRef1 ? 0 : 1]) != 0 || !pp;
+  bool need = false;
+  bool any, full = wf;  // workgroup-uniform
+  if (kRef1) {
+    // one batch: the carry's load, the zero-MV candidate straight from the
+    // planes and, without the wait's flag, thread 0's two level-2 words, all
+    // issued before the first wait on any of them
+    int cpl = 0;
+    const ptrdiff_t coff = carried ? carry_chunk(a, r, g, cpl) : -1;
+    const uint64_t tc0 = acct_now();
+    u32x4 cv = {0, 0, 0, 0};
+    if (coff >= 0) cv = carry_load(a, cpl, coff);
+    u32x2 zy = {0, 0};  // px_from_planes' loads, raw: four luma values, U, V
+    int zu = 0, zv = 0;
+    if (valid) {
+      const int l = lane_id();
+      const size_t co = (size_t)((py >> 1) + (l >> 3)) * (a.wa >> 1) + (px >> 1) + (l & 7);
+      zy = *(const u32x2_u*)&ref.y[(size_t)(py + (l >> 2)) * a.wa + px + (l & 3) * 4];
+      zu = ref.u[co], zv = ref.v[co];
+    }
+    const bool poll = threadIdx.x == 0 && !wf;
+    uint64_t w3 = 0, w2 = 0;
+    if (poll) {
+      w3 = progress_peer(a.sys, pp + min(r + 3, a.hmb - 1));
+      w2 = progress_peer(a.sys, pp + min(r + 2, a.hmb - 1));
+    }
+    // nothing of the batch is used above this line, so every load of it is
+    // issued before the first wait (the compiler otherwise unpacks the luma
+    // load, and waits for it, in front of the chroma loads)
+    asm volatile("" : "+v"(cv), "+v"(zy), "+v"(zu), "+v"(zv), "+v"(w3), "+v"(w2));
+    if (coff >= 0) carry_store(a, cpl, coff, cv);
+    Px6 zref;
+    zref.y0 = (int16_t)zy.x, zref.y1 = (int16_t)(zy.x >> 16), zref.y2 = (int16_t)zy.y, zref.y3 = (int16_t)(zy.y >> 16);
+    zref.u = zu, zref.v = zv;
+    if (carried) {
+      acct_add(a.acct, Acct::kHelperCarry, acct_now() - tc0);
+      acct_add(a.acct, Acct::kCarryBytes, 768ull * (uint64_t)min(4, a.wmb - 4 * g));
+    }
+    if (valid) {  // the source from the group's LDS copy
+      src = src_px_lds(L, wave);
+      srow = src_rows_lds(L, wave, threadIdx.x & 15);
+      sad_mad(src, zref, s.sad, s.mad);
+    }
+    need = valid && s.mad >= thr && !(CAIRO_ATTR_SKIP & 8);
+    if ((threadIdx.x & 63) == 0) L.need[wave] = need;
+    if (threadIdx.x == 0) {
+      int f = wf;
+      if (poll) {
+        f = (w3 >= want) & (w2 >= want);
+        if (f) {  // acquire what the progress words released (the loads below follow the barrier)
+          acquire_fence(a.sys);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        acct_start(a.acct, Acct::kFallbackFull, f);
+      }
+      L.full = f;
+    }
+    __syncthreads();
+    any = uni(L.need[0] | L.need[1] | L.need[2] | L.need[3]) != 0;
+    full = uni(L.full) != 0;
+    if (is) is[3] = __builtin_amdgcn_s_memrealtime();
+  } else {
+    // every wave's need is in LDS since zero_mv_older's barrier: a task none
+    // of whose waves searches polls nothing and meets no barrier
+    any = uni(L.zneed[off][0] | L.zneed[off][1] | L.zneed[off][2] | L.zneed[off][3]) != 0;
+    if (valid) {
+      src = src_px_lds(L, wave);
+      srow = src_rows_lds(L, wave, threadIdx.x & 15);
+      s.sad = L.zsad[off][wave], s.mad = L.zmad[off][wave];  // zero-MV computed at the group start
+      need = L.zneed[off][wave] != 0;
+    }
+    if (any && !wf) {  // (workgroup-uniform) the poll, as before the wait reported
+      if (threadIdx.x == 0) {
+        // both words loaded before either is tested (one round trip)
+        const uint64_t w3 = progress_peer(a.sys, pp + min(r + 3, a.hmb - 1));
+        const uint64_t w2 = progress_peer(a.sys, pp + min(r + 2, a.hmb - 1));
+        const int f = (w3 >= want) & (w2 >= want);
+        if (f) {
+          acquire_fence(a.sys);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        acct_start(a.acct, Acct::kFallbackFull, f);
+        L.full = f;
+      }
+      __syncthreads();
+      full = uni(L.full) != 0;
     }
   }
-  const bool need = valid && s.mad >= thr && !(CAIRO_ATTR_SKIP & 8);
-  if ((threadIdx.x & 63) == 0) L.need[wave] = need;
-  if (threadIdx.x == 0) {
-    // Is the reference already final over the whole window (level 2 too)?
-    // Always, in practice, for the older references (frame index-2 runs far
-    // ahead): then the window is staged in one go and the steps skip the
-    // per-step level-2 decisions and their barriers.
-    const int back = off == 1 ? 1 : 2;
-    const uint64_t* pp = back == 1 ? a.prev_progress : a.prev2_progress;
-    const uint64_t want = tagged(a.epoch - back, inter_need_cols(a, g, 2));
-    // both words loaded before either is tested (one round trip)
-    const uint64_t w3 = pp ? progress_peer(a.sys, pp + min(r + 3, a.hmb - 1)) : 0;
-    const uint64_t w2 = pp ? progress_peer(a.sys, pp + min(r + 2, a.hmb - 1)) : 0;
-    const int full = !pp || ((w3 >= want) & (w2 >= want));
-    if (full && pp) {  // acquire what the progress words released (the loads below follow the barrier)
-      acquire_fence(a.sys);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    L.full = full;
-  }
-  __syncthreads();
-  if (is && off == 1) is[3] = __builtin_amdgcn_s_memrealtime();
   acct_add(a.acct, Acct::kInterTasks, 1);
-  acct_add(a.acct, Acct::kZeroMvBytes, (off == 1 ? 768ull : 0ull) * (uint64_t)min(4, a.wmb - 4 * g));
-  if (L.need[0] | L.need[1] | L.need[2] | L.need[3]) {
-    const bool full = L.full != 0;  // workgroup-uniform
+  acct_add(a.acct, Acct::kZeroMvBytes, (kRef1 ? 768ull : 0ull) * (uint64_t)min(4, a.wmb - 4 * g));
+  if (kRef1 || any) {
+    acct_start(a.acct, Acct::kFlagSet, wf);
+    acct_start(a.acct, Acct::kFallbackPolls, !wf);
+  }
+  if (any) {
     acct_add(a.acct, Acct::kSearchedTasks, 1);
     acct_window(a.acct, 0, full ? kWinL : kLvl1Rows, 0, full ? kWinLW : kLvl1Cols);
     acct_add(a.acct, Acct::kHelperGroupStart, acct_now() - tg0);
+    acct_start(a.acct, kRef1 ? Acct::kStartRef1Searched : Acct::kStartOlderSearched, acct_now() - tg0);
+    acct_start(a.acct, Acct::kOlderSearched, kRef1 ? 0 : 1);
     ASM_MARK("group_start end");
     // (the DMA's vmcnt(0) and barrier in here are also the carry's release:
     // every wave's carry stores, issued before its DMA, are acknowledged)
@@ -1289,6 +1427,7 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
         lvl2_open = (m4 >> 2) != 0;
         if (m) {
           if (is) is[5] = __builtin_amdgcn_s_memrealtime();
+          acct_start(a.acct, Acct::kLvl2Runs, 1);
           // (no deblock meanwhile: rare, and its inputs' registers would spill
           // the search state live here)
           helper_wait<false>(a, off == 1 ? 1 : 2, r, min(r + ((m & 2) ? 3 : 2), a.hmb - 1), inter_need_cols(a, g, 2),
@@ -1401,6 +1540,10 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
+  if (!any) {
+    acct_start(a.acct, kRef1 ? Acct::kStartRef1Idle : Acct::kStartOlderIdle, acct_now() - tg0);
+    acct_start(a.acct, kRef1 ? Acct::kRef1Idle : Acct::kOlderIdle, 1);
+  }
   if (is && off == 1) is[10] = __builtin_amdgcn_s_memrealtime();
   if (valid && (threadIdx.x & 63) == 0) {
     // two tagged granules (kernels.h pack_inter_desc): the coder polls them,
@@ -1413,8 +1556,10 @@ __device__ __forceinline__ void inter_task(FA& a0, int r, int g, int off, InterL
   }
   // the next task rewrites the window: every wave is done reading it (its
   // LDS reads returned); the records' stores stay in flight (each one waits
-  // about 3.5 us for its write-through acknowledgement)
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // about 3.5 us for its write-through acknowledgement).  An older task
+  // that searched nothing read no window and wrote no LDS word: no barrier.
+  if (kRef1 || any) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  return any;
 }
 
 // ---------------------------------------------------------------------------
@@ -1936,7 +2081,7 @@ constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0) expcnt(7) lgkmcnt(15) (g
 
 // A macroblock's end waits only for its coefficient stores (which its info
 // granule releases to the deblock and, through its progress, to the next
-// frame's carry of the group: carry_group), not for the pixel-granule and
+// frame's carry of the group: carry_chunk), not for the pixel-granule and
 // table stores
 // issued after them: vmcnt retires in order, so wave w waits until no more
 // than the stores it issued after its last coefficient store are
@@ -2687,7 +2832,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         d.q_index = 0;
         d.variance = 0;
         // Inter frames: the row's helper carried them before it stored the
-        // group's records (carry_group), so there is nothing to load, store
+        // group's records (carry_chunk), so there is nothing to load, store
         // or drain here.  Intra frames (their helpers only carry the
         // dependency) keep the carry below; a decode launch reads coef.
         if (!kDecode && (!ap->inter || CAIRO_CODER_CARRY)) {  // workgroup-uniform
@@ -2709,7 +2854,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       // pairs (lane, lane^1) of each 8x8 block as granules.  No drain before
       // them: the coefficient stores only have to be visible to whoever
       // observes the info granule below (the deblock, and through its
-      // progress the next frame's helper, which carries them: carry_group),
+      // progress the next frame's helper, which carries them: carry_chunk),
       // which is stored after the drain.  A copy macroblock of an inter frame
       // stores no coefficient; its drain below then waits for nothing it
       // issued here (the helper's carry was acknowledged before the records).
@@ -2811,28 +2956,38 @@ __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* fla
     // progress word, tagged epoch-2, also covers frame index-3: that frame's
     // row r+2 waited for index-3's row r+4 over a wider window), so these
     // searches fill what used to be the wait for the previous frame.
+    const uint64_t tgrp = acct_now();
+    bool searched = false;  // accounting: some task of the group searched
     if (a.inter) group_source(a, r, g, L.inter);
     if (a.inter && a.nref >= 2) {
-      helper_wait(a, 2, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag);
+      // (the wait also says whether the whole window is final: §4.12)
+      helper_wait(a, 2, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag, &L.inter.wfull[1], true,
+                  g);
       const uint64_t ts = acct_now();
       zero_mv_older(a, r, g, L.inter);
-      for (int off = 2; off <= a.nref; off++) inter_task(a, r, g, off, L.inter, L.db, st, flag, is);
+      for (int off = 2; off <= a.nref; off++)
+        searched |= inter_task<false>(a, r, g, off, L.inter, L.db, st, flag, is);
       acct_add(a.acct, Acct::kHelperSearch, acct_now() - ts);
     }
     // level 1 of the group's window in the previous frame; deblock meanwhile
     // (leaving the chunks to the catch-up after the group's records instead
     // measured neutral in round 4; catch-ups between the older references'
     // searches too, in round 5)
-    helper_wait(a, 1, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag);
+    helper_wait(a, 1, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag,
+                &L.inter.wfull[0], a.inter != 0, g);
     if (is) is[1] = __builtin_amdgcn_s_memrealtime();
     trace(tr, 3, 50);
     if (a.inter) {
-      // the group's output_cache carry, right after the wait (which covers
-      // coef_prev: carry_group); released by inter_task before the records
-      const bool carried = carry_group(a, r, g);
+      // the group's output_cache carry, after the wait (which covers
+      // coef_prev: carry_chunk), inside inter_task's first batch of loads;
+      // released by inter_task before the records
       const uint64_t ts = acct_now();
-      inter_task(a, r, g, 1, L.inter, L.db, st, flag, is, carried);
+      searched |= inter_task<true>(a, r, g, 1, L.inter, L.db, st, flag, is, carry_wanted(a));
       acct_add(a.acct, Acct::kHelperSearch, acct_now() - ts);
+      if (!searched) {
+        acct_start(a.acct, Acct::kIdleGroups, 1);
+        acct_start(a.acct, Acct::kIdleGroupTime, acct_now() - tgrp);
+      }
     } else if (tid == 0) {  // intra frame: carry the dependency only
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

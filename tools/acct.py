@@ -100,6 +100,26 @@ def main():
     helper["carry"] = round(us(c["helper_carry"]) / groups, 3)  # first load .. last store issued; inside "rest"
     # a searched inter task's entry to its first window DMA (inside "search"), per searched task
     helper["group_start_per_searched_task"] = round(us(c["helper_group_start"]) / max(c["searched_tasks"], 1), 3)
+    # the group start by reference and by searched / not: a task's entry to its first window
+    # DMA, or to its record stores when nothing searches, per task of that kind; what the wait's flag said for
+    # the tasks that needed it; the groups in which no task searched (a library from before §4.12 has none of
+    # these counters and reads zeros)
+    if "idle_groups" in c:
+        ref1_searched = c["searched_tasks"] - c["older_searched"]
+        asked = max(c["flag_set"] + c["fallback_polls"], 1)
+        helper["group_start"] = {
+            "older_searched_us": round(us(c["start_older_searched"]) / max(c["older_searched"], 1), 3),
+            "ref1_searched_us": round(us(c["start_ref1_searched"]) / max(ref1_searched, 1), 3),
+            "older_idle_us": round(us(c["start_older_idle"]) / max(c["older_idle"], 1), 3),
+            "ref1_idle_us": round(us(c["start_ref1_idle"]) / max(c["ref1_idle"], 1), 3),
+            "tasks": {"older_searched": c["older_searched"], "ref1_searched": ref1_searched,
+                      "older_idle": c["older_idle"], "ref1_idle": c["ref1_idle"]},
+            "flag_set_frac": round(c["flag_set"] / asked, 4),
+            "fallback_polls_frac": round(c["fallback_polls"] / asked, 4),
+            "fallback_found_full_frac": round(c["fallback_full"] / max(c["fallback_polls"], 1), 4),
+            "lvl2_runs_per_searched_task": round(c["lvl2_runs"] / max(c["searched_tasks"], 1), 4),
+            "idle_group_frac": round(c["idle_groups"] / groups, 4),
+            "idle_group_us": round(us(c["idle_group_time"]) / max(c["idle_groups"], 1), 3)}
     helper["deblock_phases"] ={k: round(us(c[k]) / groups, 3) for k in ("db_inputs", "db_filter", "db_write")}
     helper["chunks_per_group"] = round(c["helper_chunks"] / groups, 3)
     mb = 1e6
