@@ -50,6 +50,10 @@ EVX_ERROR_INVALID_ARGS = 1
 # Pixel formats (include/cairo_amd.h CAIRO_FMT_*): a frame is one contiguous
 # uint8 buffer with a row pitch in bytes (0: tight); see frame_layout.
 FMT_RGB24, FMT_BGR24, FMT_I420, FMT_NV12 = range(4)
+# Colour description of an I420 / NV12 frame (include/cairo_amd.h CAIRO_RANGE_*,
+# CAIRO_MATRIX_*): (RANGE_FULL, MATRIX_BT601) is the codec's own space.
+RANGE_FULL, RANGE_LIMITED = 0, 1
+MATRIX_BT601, MATRIX_BT709 = 0, 1
 # Per-frame metrics and kept reconstructions (include/cairo_amd.h, cairo_ctx_set_metrics)
 METRIC_SSE, METRIC_SSIM, KEEP_RECON = 1, 2, 4
 
@@ -94,6 +98,12 @@ def lib() -> ctypes.CDLL:
         "cairo_ctx_decode_frame_fmt": (I, [P, P, P, U, I, U, P]),
         "cairo_frame_layout": (I, [I, U, U, U, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(U)]),
         "cairo_kat_convert": (I, [I, I, U, U, U, P, P, P, P, I]),
+        "cairo_kat_convert_color": (I, [I, I, I, I, U, U, U, P, P, P, P, I]),
+        "cairo_color_coefs": (I, [I, I, I, P, ctypes.POINTER(ctypes.c_int32)]),
+        "cairo_ctx_set_input_color": (I, [P, I, I]),
+        "cairo_ctx_set_output_color": (I, [P, I, I]),
+        "evx_encoder_set_input_color": (I, [P, I, I]),
+        "evx_decoder_set_output_color": (I, [P, I, I]),
         "cairo_stream_submit_fmt": (I, [P, P, I, I, U, U, U, U, ctypes.POINTER(I)]),
         "evx_encoder_set_input_format": (I, [P, I, U]),
         "evx_decoder_set_output_format": (I, [P, I, U]),
@@ -224,6 +234,18 @@ def frame_layout(fmt: int, w: int, h: int, pitch: int = 0):
     if not ok or lib().cairo_frame_layout(int(fmt), int(w), int(h), int(pitch), ctypes.byref(nb), ctypes.byref(tight)):
         raise ValueError(f"no frame layout for format {fmt}, {w}x{h}, pitch {pitch}")
     return nb.value, tight.value
+
+
+def color_coefs(direction: int, range: int, matrix: int):
+    """-> (k, oy): the 3x3 int32 table (2^14 fixed point) and the luma offset
+    the kernels use for a colour description (cairo_color_coefs); direction 0:
+    described YUV to the codec's full-range BT.601, 1: the reverse.  ValueError
+    for unknown values.  No device needed."""
+    k, oy = np.zeros(9, np.int32), ctypes.c_int32()
+    ok = all(isinstance(x, (int, np.integer)) and -2 ** 31 <= x < 2 ** 31 for x in (direction, range, matrix))
+    if not ok or lib().cairo_color_coefs(int(direction), int(range), int(matrix), _ptr(k), ctypes.byref(oy)):
+        raise ValueError(f"no colour description (direction {direction}, range {range}, matrix {matrix})")
+    return k.reshape(3, 3), oy.value
 
 
 def split_frame(buf: np.ndarray, fmt: int, w: int, h: int, pitch: int = 0):
@@ -572,6 +594,17 @@ class Context:
         if flags is None:
             flags = (METRIC_SSE if sse else 0) | (METRIC_SSIM if ssim else 0) | (KEEP_RECON if keep_recon else 0)
         _ck(self.L.cairo_ctx_set_metrics(self.h, flags), "cairo_ctx_set_metrics")
+
+    def set_input_color(self, range: int, matrix: int) -> None:
+        """The colour description (RANGE_*, MATRIX_*) of the I420 / NV12 frames
+        submitted from now on, also through a Stream; recorded per frame at
+        submit.  RGB frames ignore it.  Survives reset()."""
+        _ck(self.L.cairo_ctx_set_input_color(self.h, range, matrix), "cairo_ctx_set_input_color")
+
+    def set_output_color(self, range: int, matrix: int) -> None:
+        """The colour description fetch_recon and cairo_ctx_decode_frame_fmt
+        write I420 / NV12 frames in from now on."""
+        _ck(self.L.cairo_ctx_set_output_color(self.h, range, matrix), "cairo_ctx_set_output_color")
 
     def frame_metrics(self, ticket: int) -> dict:
         """Metrics of a waited, unreleased frame: the raw cairo_frame_metrics
@@ -1071,6 +1104,11 @@ class Encoder:
         _ck(self.L.evx_encoder_set_input_format(self.h, fmt, pitch), "set_input_format")
         self._fmt, self._pitch = fmt, pitch
 
+    def set_input_color(self, range: int, matrix: int) -> None:
+        """The colour description (RANGE_*, MATRIX_*) of the I420 / NV12 frames
+        encode() reads from now on; callable between frames."""
+        _ck(self.L.evx_encoder_set_input_color(self.h, range, matrix), "set_input_color")
+
     def set_metrics(self, sse: bool = True, ssim: bool = True) -> None:
         """Per-frame metrics for the frames encode() codes from now on."""
         _ck(self.L.evx_encoder_set_metrics(self.h, (METRIC_SSE if sse else 0) | (METRIC_SSIM if ssim else 0)),
@@ -1144,6 +1182,11 @@ class Decoder:
         pitch in bytes, 0: tight); callable between frames."""
         _ck(self.L.evx_decoder_set_output_format(self.h, fmt, pitch), "set_output_format")
         self._fmt, self._pitch = fmt, pitch
+
+    def set_output_color(self, range: int, matrix: int) -> None:
+        """The colour description (RANGE_*, MATRIX_*) decode() writes I420 /
+        NV12 frames in from now on; callable between frames."""
+        _ck(self.L.evx_decoder_set_output_color(self.h, range, matrix), "set_output_color")
 
     def decode(self, bs: "BitStream", width: int, height: int, out: np.ndarray | None = None) -> np.ndarray:
         """Decode [header +] one frame record of bs (emptied afterwards) -> RGB

@@ -215,6 +215,12 @@ struct cairo_ctx {
   // one.  pend_hpitch: the pitch of a host source still to upload (flush).
   uint8_t pend_fmt[kMaxBatch] = {};
   uint32_t pend_pitch[kMaxBatch] = {}, pend_hpitch[kMaxBatch] = {};
+  // Colour descriptions (cairo_ctx_set_input_color / _output_color, DESIGN
+  // §4.13) as kernels.h color_index values: in_col is recorded per frame at
+  // submit (pend_col; 0 for an RGB frame), out_col is read when a frame is
+  // written as I420 / NV12.  Neither is touched by cairo_ctx_reset.
+  uint8_t pend_col[kMaxBatch] = {};
+  int in_col = 0, out_col = 0;
   // A scaled frame (cairo_ctx_submit_scaled) is a device frame whose f.rgb is
   // its staging slot, tight; its source and geometry wait here for the launch,
   // whose k_scale_batch fills the slot before the convert reads it.
@@ -684,7 +690,8 @@ int flush(cairo_ctx* c) {
   }
   // A launch of tight RGB24 frames keeps k_convert_batch, whose behaviour
   // beside the running launch is measured; any other
-  // layout in the launch takes all of its frames through k_convert_fmt_batch.
+  // layout in the launch takes all of its frames through k_convert_fmt_batch
+  // (a colour description belongs to a YUV frame, which is never tight RGB24).
   bool tight_rgb = true;
   for (int i = 0; i < e.nframes; i++)
     tight_rgb &= !ca.rgb[i] || (c->pend_fmt[i] == CAIRO_FMT_RGB24 && c->pend_pitch[i] == 3 * c->w);
@@ -693,7 +700,8 @@ int flush(cairo_ctx* c) {
   } else {
     ConvertFmtArgs cf{};
     cf.c = ca;
-    for (int i = 0; i < e.nframes; i++) cf.fmt[i] = c->pend_fmt[i], cf.pitch[i] = c->pend_pitch[i];
+    for (int i = 0; i < e.nframes; i++)
+      cf.fmt[i] = c->pend_fmt[i], cf.pitch[i] = c->pend_pitch[i], cf.col[i] = c->pend_col[i];
     CK(launch_convert_fmt_batch(cf, st));
   }
   CK(hipEventRecord(c->fdesc_done[fslot], st));  // fh has been read
@@ -1214,6 +1222,7 @@ static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int
   c->pend_fmt[c->npend] = (uint8_t)fmt;
   c->pend_pitch[c->npend] = rgb_on_device && pitch && !scaled ? pitch : tight;  // a host frame is staged tight
   c->pend_hpitch[c->npend] = pitch;
+  c->pend_col[c->npend] = fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_NV12 ? (uint8_t)c->in_col : 0;
   c->pend_scaled[c->npend] = scaled != nullptr;
   if (scaled) {  // scaled into the slot at launch, tight
     f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
@@ -1501,7 +1510,7 @@ static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef,
     if (fmt < 0)
       r = fail(launch_yuv_to_rgb(recon, (int)c->wa, (int)c->w, (int)c->h, drgb, st), "launch_yuv_to_rgb");
     else
-      r = fail(launch_planes_to_fmt(recon, (int)c->wa, (int)c->w, (int)c->h, fmt, tight, drgb, st),
+      r = fail(launch_planes_to_fmt(recon, (int)c->wa, (int)c->w, (int)c->h, fmt, tight, drgb, c->out_col, st),
                "launch_planes_to_fmt");
     if (r == kSuccess)
       r = fail(hipMemcpyAsync(s.err, c->sticky, TimeoutInfo::kWords * sizeof(int32_t), hipMemcpyDeviceToHost, st),
@@ -1526,6 +1535,25 @@ int cairo_ctx_decode_frame_fmt(cairo_ctx* c, const uint8_t* table, const int16_t
                                uint32_t pitch, uint8_t* out) {
   if (fmt < 0) return kInvalidArg;
   return decode_frame(c, table, coef, index, fmt, pitch, out);
+}
+
+static bool color_known(int range, int matrix) {
+  return (range == CAIRO_RANGE_FULL || range == CAIRO_RANGE_LIMITED) &&
+         (matrix == CAIRO_MATRIX_BT601 || matrix == CAIRO_MATRIX_BT709);
+}
+
+int cairo_ctx_set_input_color(cairo_ctx* c, int range, int matrix) {
+  if (!c || !color_known(range, matrix)) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->in_col = color_index(range, matrix);  // frames already submitted keep theirs (pend_col)
+  return kSuccess;
+}
+
+int cairo_ctx_set_output_color(cairo_ctx* c, int range, int matrix) {
+  if (!c || !color_known(range, matrix)) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->out_col = color_index(range, matrix);
+  return kSuccess;
 }
 
 int cairo_ctx_max_workgroups(const cairo_ctx* c) { return c ? c->max_rows : 0; }
@@ -1681,7 +1709,8 @@ int cairo_ctx_fetch_recon(cairo_ctx* c, int ticket, int fmt, uint32_t pitch, uin
   // wait, and the next upload into it follows the ticket's release
   const int slot = ticket % c->stages;
   uint8_t* staged = c->rgb + (size_t)slot * c->w * c->h * 3;
-  CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, fmt, tight, staged, c->fs));
+  CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, fmt, tight, staged,
+                          c->out_col, c->fs));
   const int r = download_frame(c, out, staged, fmt, pitch, tight, frame_bytes, c->fs);
   if (r) return r;
   CK(hipStreamSynchronize(c->fs));

@@ -81,6 +81,16 @@ class gpu_decoder : public evx1_decoder {
     pitch_ = pitch;
     return EVX_SUCCESS;
   }
+  // The colour description decode() writes I420 / NV12 frames in (between
+  // frames too; RGB frames ignore it).
+  evx_status set_output_color(int range, int matrix) {
+    int32_t k[9], oy;
+    if (cairo_color_coefs(1, range, matrix, k, &oy)) return EVX_ERROR_INVALIDARG;
+    if (initialized_ && cairo_ctx_set_output_color(ctx_, range, matrix)) return EVX_ERROR_INVALIDARG;
+    range_ = range;
+    matrix_ = matrix;
+    return EVX_SUCCESS;
+  }
 
  private:
   // initialize (evx1dec.cpp:43-73) with verify_header (common.cpp:25-43).  The
@@ -103,6 +113,7 @@ class gpu_decoder : public evx1_decoder {
     wmb_ = wa_ / 16;
     hmb_ = ha_ / 16;
     if (cairo_ctx_create_ex(width_, height_, ring_, device_, 2, &ctx_)) return EVX_ERROR_HARDWAREFAIL;  // synchronous: 2 slots
+    (void)cairo_ctx_set_output_color(ctx_, range_, matrix_);  // (checked by set_output_color)
     table_ = (cairo::BlockDesc *)calloc((size_t)wmb_ * hmb_, sizeof(cairo::BlockDesc));
     coef_ = (int16 *)calloc((size_t)wa_ * ha_ * 3 / 2, sizeof(int16));
     if (!table_ || !coef_) {
@@ -125,6 +136,7 @@ class gpu_decoder : public evx1_decoder {
   int device_ = 0;
   int fmt_ = CAIRO_FMT_RGB24;  // output layout (set_output_format)
   uint32 pitch_ = 0;
+  int range_ = CAIRO_RANGE_FULL, matrix_ = CAIRO_MATRIX_BT601;  // set_output_color
   cairo_ctx *ctx_ = nullptr;
   cairo::BlockDesc *table_ = nullptr;
   int16 *coef_ = nullptr;
@@ -162,6 +174,9 @@ int evx_decoder_set_device(void *dec, int device) {
 }
 int evx_decoder_set_output_format(void *dec, int fmt, uint32_t pitch) {
   return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_output_format(fmt, pitch);
+}
+int evx_decoder_set_output_color(void *dec, int range, int matrix) {
+  return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_output_color(range, matrix);
 }
 
 }  // extern "C"

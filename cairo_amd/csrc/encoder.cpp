@@ -205,6 +205,16 @@ class gpu_encoder : public evx1_encoder {
     pitch_ = pitch;
     return EVX_SUCCESS;
   }
+  // The colour description of the I420 / NV12 images encode() reads (between
+  // frames too; RGB images ignore it).
+  evx_status set_input_color(int range, int matrix) {
+    int32_t k[9], oy;
+    if (cairo_color_coefs(0, range, matrix, k, &oy)) return EVX_ERROR_INVALIDARG;
+    if (initialized_ && cairo_ctx_set_input_color(ctx_, range, matrix)) return EVX_ERROR_INVALIDARG;
+    range_ = range;
+    matrix_ = matrix;
+    return EVX_SUCCESS;
+  }
   // CAIRO_METRIC_* for the frames coded from now on (between frames too; the
   // synchronous encode() leaves no frame in flight), and the last frame's.
   evx_status set_metrics(int flags) {
@@ -236,6 +246,7 @@ class gpu_encoder : public evx1_encoder {
     // the GPU precodes the entropy feed; only the arithmetic coder runs here
     if (cairo_ctx_set_outputs(ctx_, CAIRO_OUT_FEED)) return EVX_ERROR_HARDWAREFAIL;
     if (metrics_ && cairo_ctx_set_metrics(ctx_, metrics_)) return EVX_ERROR_HARDWAREFAIL;
+    if (cairo_ctx_set_input_color(ctx_, range_, matrix_)) return EVX_ERROR_HARDWAREFAIL;
     const size_t mbs = (size_t)((width + 15) / 16) * ((height + 15) / 16);
     last_table_ = (uint8 *)calloc(mbs, 16);
     if (!last_table_) return EVX_ERROR_OUTOFMEMORY;
@@ -253,6 +264,7 @@ class gpu_encoder : public evx1_encoder {
   int device_ = 0;
   int fmt_ = CAIRO_FMT_RGB24;  // input layout (set_input_format)
   uint32 pitch_ = 0;
+  int range_ = CAIRO_RANGE_FULL, matrix_ = CAIRO_MATRIX_BT601;  // set_input_color
   cairo_ctx *ctx_ = nullptr;
   uint8 *last_table_ = nullptr;
   int metrics_ = 0;  // set_metrics
@@ -300,6 +312,9 @@ int evx_encoder_set_device(void *enc, int device) {
 }
 int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch) {
   return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_format(fmt, pitch);
+}
+int evx_encoder_set_input_color(void *enc, int range, int matrix) {
+  return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_color(range, matrix);
 }
 
 int evx_encoder_set_metrics(void *enc, int flags) {

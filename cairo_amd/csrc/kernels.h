@@ -443,17 +443,32 @@ hipError_t launch_convert_batch(const ConvertArgs& c, hipStream_t s);
 // The same launch when any of its frames is not tight RGB24 (pixfmt.hip):
 // every frame carries its format (CAIRO_FMT_*) and row pitch in bytes, and is
 // read in place at any byte alignment.  c.wa is the pitch of the planes.
+//
+// A colour description (CAIRO_RANGE_*, CAIRO_MATRIX_*; include/cairo_amd.h) of
+// an I420 / NV12 frame is carried as the index range + 2 * matrix: 0 is the
+// codec's own space (the identity), 1 LIMITED with BT601 (a diagonal map: no
+// luma / chroma coupling), 2 and 3 the BT709 ones (the full map).  ColorMap is
+// one direction of one description: the nonzero 2^14 fixed-point coefficients
+// of [k00 k01 k02; 0 k11 k12; 0 k21 k22] and the luma offset oy.
+constexpr int kColorMaps = 4;
+struct ColorMap {
+  int32_t k00, k01, k02, k11, k12, k21, k22, oy;
+};
+__host__ __device__ inline int color_index(int range, int matrix) { return range + 2 * matrix; }
 struct ConvertFmtArgs {
   ConvertArgs c;
   uint32_t pitch[kMaxBatch];
   uint8_t fmt[kMaxBatch];
+  uint8_t col[kMaxBatch];     // colour description index of a YUV frame (0 for an RGB one)
+  ColorMap map[kColorMaps];   // the input maps by index; filled by launch_convert_fmt_batch
 };
 hipError_t launch_convert_fmt_batch(const ConvertFmtArgs& c, hipStream_t s);
 // Plane set src (rows of plane_pitch elements) as a w x h frame of format fmt
 // with the given row pitch (bytes) at dst; bytes outside the image's rows are
-// not written.
+// not written.  col: the colour description index of the frame written (used
+// for I420 / NV12 only).
 hipError_t launch_planes_to_fmt(PlaneSet src, int plane_pitch, int w, int h, int fmt, uint32_t pitch, uint8_t* dst,
-                                hipStream_t s);
+                                int col, hipStream_t s);
 // The pipelined encode engine: inter search, macroblock rows (intra search,
 // classify, transform, quantize, reconstruct) and in-loop deblock.
 hipError_t launch_engine(const EngineArgs& e, hipStream_t s);

@@ -13,6 +13,12 @@
 // byte accesses where its row start is not aligned or where it is cut by the
 // right edge; nothing outside width x height is read or written on either
 // side, so the pitch padding of a destination keeps its bytes.
+//
+// I420 and NV12 frames carry a colour description (cairo_amd.h CAIRO_RANGE_*,
+// CAIRO_MATRIX_*).  Both strip functions take its mode as a
+// template parameter, chosen once per workgroup like the format: identity (the
+// codec's own space: the code as it was), diagonal (LIMITED with BT601: no
+// chroma term in the luma) and full.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -43,6 +49,50 @@ __device__ __forceinline__ uint32_t sat8(int32_t v) {
   return r;
 }
 __device__ __forceinline__ uint32_t clamp8(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// Modes of a colour description index (kernels.h color_index).
+constexpr int kColorIdentity = 0, kColorDiagonal = 1, kColorFull = 2;
+constexpr int kColorShift = 14, kColorHalf = 1 << (kColorShift - 1);
+
+// A sample of a colour map: one rounding, clamped to 0..255 and, like sat8,
+// pinned to a register of its own before anything packs it.
+__device__ __forceinline__ uint32_t color8(int32_t acc) {
+  uint32_t r = clamp8(acc >> kColorShift);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(r));
+#endif
+  return r;
+}
+
+// The map of one strip on its 8-bit samples, in place: y8[dy][k] with the
+// chroma sample k >> 1, then the chroma samples themselves (which never depend
+// on luma).  IN: the input direction (oy leaves Y before the product), else
+// the output direction (oy joins it after).
+template <int MODE, bool IN>
+__device__ __forceinline__ void color_strip(const ColorMap& m, int (&y8)[2][kStrip], int (&u8)[kStrip / 2],
+                                            int (&v8)[kStrip / 2]) {
+  static_assert(MODE == kColorDiagonal || MODE == kColorFull, "the identity has no map");
+  const int ybias = (IN ? -m.k00 * m.oy : (m.oy << kColorShift)) + kColorHalf;
+  constexpr int cbias = (128 << kColorShift) + kColorHalf;
+#pragma unroll
+  for (int k = 0; k < kStrip / 2; k++) {
+    const int d1 = u8[k] - 128, d2 = v8[k] - 128;
+    int cy = ybias;
+    if constexpr (MODE == kColorFull) cy += m.k01 * d1 + m.k02 * d2;
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++) {
+      y8[dy][2 * k] = (int)color8(m.k00 * y8[dy][2 * k] + cy);
+      y8[dy][2 * k + 1] = (int)color8(m.k00 * y8[dy][2 * k + 1] + cy);
+    }
+    if constexpr (MODE == kColorFull) {
+      u8[k] = (int)color8(m.k11 * d1 + m.k12 * d2 + cbias);
+      v8[k] = (int)color8(m.k21 * d1 + m.k22 * d2 + cbias);
+    } else {
+      u8[k] = (int)color8(m.k11 * d1 + cbias);
+      v8[k] = (int)color8(m.k22 * d2 + cbias);
+    }
+  }
+}
 
 // Byte k of a little-endian dword array.
 template <int W>
@@ -125,11 +175,14 @@ __device__ __forceinline__ void load_i16(const int16_t* p, int n, int (&v)[N]) {
 // ---------------------------------------------------------------------------
 // Input side: strip sx of row pair qy of one frame -> its source planes.
 // RGB24 / BGR24: the arithmetic of k_convert_batch (convert.cpp:11-14, 30-73).
-// I420 / NV12: the codec's own full-range BT.601 samples, Y + 16, U, V.
+// I420 / NV12: the codec's own full-range BT.601 samples, Y + 16, U, V; under
+// a colour description, the same rule on the mapped samples.
 // ---------------------------------------------------------------------------
-template <int FMT>
+template <int FMT, int MODE = kColorIdentity>
 __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pitch, const PlaneSet& in, int w, int h,
-                                              int wa, int sx, int qy) {
+                                              int wa, int sx, int qy, const ColorMap& m) {
+  static_assert(MODE == kColorIdentity || FMT == CAIRO_FMT_I420 || FMT == CAIRO_FMT_NV12,
+                "a colour description applies to the YUV formats");
   const int x0 = sx * kStrip;
   const int n = min(kStrip, w - x0);  // luma columns of this strip inside the image: 2, 4, 6 or 8
   const int nc = n >> 1;
@@ -157,7 +210,7 @@ __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pit
       uint32_t py[2];
       load_bytes<8>(frame + (size_t)(2 * qy + dy) * pitch + x0, n, py);
 #pragma unroll
-      for (int k = 0; k < kStrip; k++) yv[dy][k] = byte_of(py, k) + 16;
+      for (int k = 0; k < kStrip; k++) yv[dy][k] = byte_of(py, k) + (MODE == kColorIdentity ? 16 : 0);
     }
     const uint8_t* chroma = frame + (size_t)pitch * h;
     if constexpr (FMT == CAIRO_FMT_I420) {
@@ -173,6 +226,13 @@ __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pit
       load_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
 #pragma unroll
       for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(puv, 2 * k), vv[k] = byte_of(puv, 2 * k + 1);
+    }
+    if constexpr (MODE != kColorIdentity) {
+      color_strip<MODE, true>(m, yv, uv, vv);
+#pragma unroll
+      for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int k = 0; k < kStrip; k++) yv[dy][k] += 16;
     }
   }
 #pragma unroll
@@ -197,22 +257,41 @@ __global__ __launch_bounds__(kFmtThreads) void k_convert_fmt_batch(ConvertFmtArg
   if (!frame || sx * kStrip >= e.c.w) return;
   const PlaneSet in = e.c.in[blockIdx.z];
   const uint32_t pitch = e.pitch[blockIdx.z];
-  switch (e.fmt[blockIdx.z]) {  // uniform over the workgroup
-    case CAIRO_FMT_RGB24: convert_strip<CAIRO_FMT_RGB24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
-    case CAIRO_FMT_BGR24: convert_strip<CAIRO_FMT_BGR24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
-    case CAIRO_FMT_I420: convert_strip<CAIRO_FMT_I420>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
-    default: convert_strip<CAIRO_FMT_NV12>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy); break;
+  const int col = e.col[blockIdx.z] & (kColorMaps - 1);
+  const ColorMap m = e.map[col];
+  switch (e.fmt[blockIdx.z]) {  // uniform over the workgroup, as is col
+    case CAIRO_FMT_RGB24: convert_strip<CAIRO_FMT_RGB24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
+    case CAIRO_FMT_BGR24: convert_strip<CAIRO_FMT_BGR24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
+    case CAIRO_FMT_I420:
+      if (col == 0)
+        convert_strip<CAIRO_FMT_I420>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
+      else if (col == 1)
+        convert_strip<CAIRO_FMT_I420, kColorDiagonal>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
+      else
+        convert_strip<CAIRO_FMT_I420, kColorFull>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
+      break;
+    default:
+      if (col == 0)
+        convert_strip<CAIRO_FMT_NV12>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
+      else if (col == 1)
+        convert_strip<CAIRO_FMT_NV12, kColorDiagonal>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
+      else
+        convert_strip<CAIRO_FMT_NV12, kColorFull>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
+      break;
   }
 }
 
 // ---------------------------------------------------------------------------
 // Output side: strip sx of row pair qy of a plane set -> the pitched frame.
 // RGB24 / BGR24: the arithmetic of k_yuv_to_rgb (convert.cpp:16-19, 162-223).
-// I420 / NV12: clamp(Y - 16), clamp(U), clamp(V) of the int16 samples.
+// I420 / NV12: clamp(Y - 16), clamp(U), clamp(V) of the int16 samples; under a
+// colour description those 8-bit samples are then mapped.
 // ---------------------------------------------------------------------------
-template <int FMT>
+template <int FMT, int MODE = kColorIdentity>
 __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w, int h, uint32_t pitch, uint8_t* dst,
-                                             int sx, int qy) {
+                                             int sx, int qy, const ColorMap& m) {
+  static_assert(MODE == kColorIdentity || FMT == CAIRO_FMT_I420 || FMT == CAIRO_FMT_NV12,
+                "a colour description applies to the YUV formats");
   const int x0 = sx * kStrip;
   const int n = min(kStrip, w - x0);
   const int nc = n >> 1;
@@ -240,11 +319,24 @@ __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w,
       store_bytes<24>(dst + (size_t)(2 * qy + dy) * pitch + 3 * x0, 3 * n, px);
     }
   } else {
+    if constexpr (MODE != kColorIdentity) {  // clamp to 8 bits as the identity does, then map
+#pragma unroll
+      for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int k = 0; k < kStrip; k++) yv[dy][k] = (int)clamp8(yv[dy][k] - 16);
+#pragma unroll
+      for (int k = 0; k < kStrip / 2; k++) uv[k] = (int)clamp8(uv[k]), vv[k] = (int)clamp8(vv[k]);
+      color_strip<MODE, false>(m, yv, uv, vv);
+    }
+    // the bytes to pack: clamped here, or the map's clamped and pinned samples
+    auto yb = [&](int dy, int k) { return MODE == kColorIdentity ? clamp8(yv[dy][k] - 16) : (uint32_t)yv[dy][k]; };
+    auto ub = [&](int k) { return MODE == kColorIdentity ? clamp8(uv[k]) : (uint32_t)uv[k]; };
+    auto vb = [&](int k) { return MODE == kColorIdentity ? clamp8(vv[k]) : (uint32_t)vv[k]; };
 #pragma unroll
     for (int dy = 0; dy < 2; dy++) {
       uint32_t py[2] = {};
 #pragma unroll
-      for (int k = 0; k < kStrip; k++) py[k >> 2] |= clamp8(yv[dy][k] - 16) << (8 * (k & 3));
+      for (int k = 0; k < kStrip; k++) py[k >> 2] |= yb(dy, k) << (8 * (k & 3));
       store_bytes<8>(dst + (size_t)(2 * qy + dy) * pitch + x0, n, py);
     }
     uint8_t* chroma = dst + (size_t)pitch * h;
@@ -253,29 +345,64 @@ __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w,
       uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
       uint32_t pu[1] = {}, pv[1] = {};
 #pragma unroll
-      for (int k = 0; k < kStrip / 2; k++) pu[0] |= clamp8(uv[k]) << (8 * k), pv[0] |= clamp8(vv[k]) << (8 * k);
+      for (int k = 0; k < kStrip / 2; k++) pu[0] |= ub(k) << (8 * k), pv[0] |= vb(k) << (8 * k);
       store_bytes<4>(up, nc, pu);
       store_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
     } else {
       uint32_t puv[2] = {};
 #pragma unroll
       for (int k = 0; k < kStrip / 2; k++)
-        puv[k >> 1] |= (clamp8(uv[k]) | (clamp8(vv[k]) << 8)) << (16 * (k & 1));
+        puv[k >> 1] |= (ub(k) | (vb(k) << 8)) << (16 * (k & 1));
       store_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
     }
   }
 }
 
+// col / m: the colour description index of the frame written and its output
+// map (used for I420 / NV12 only).
 __global__ __launch_bounds__(kFmtThreads) void k_planes_to_fmt(PlaneSet src, int sp, int w, int h, int fmt,
-                                                               uint32_t pitch, uint8_t* dst) {
+                                                               uint32_t pitch, uint8_t* dst, int col, ColorMap m) {
   const int sx = blockIdx.x * kFmtThreads + threadIdx.x, qy = blockIdx.y;
   if (sx * kStrip >= w) return;
   switch (fmt) {
-    case CAIRO_FMT_RGB24: planes_strip<CAIRO_FMT_RGB24>(src, sp, w, h, pitch, dst, sx, qy); break;
-    case CAIRO_FMT_BGR24: planes_strip<CAIRO_FMT_BGR24>(src, sp, w, h, pitch, dst, sx, qy); break;
-    case CAIRO_FMT_I420: planes_strip<CAIRO_FMT_I420>(src, sp, w, h, pitch, dst, sx, qy); break;
-    default: planes_strip<CAIRO_FMT_NV12>(src, sp, w, h, pitch, dst, sx, qy); break;
+    case CAIRO_FMT_RGB24: planes_strip<CAIRO_FMT_RGB24>(src, sp, w, h, pitch, dst, sx, qy, m); break;
+    case CAIRO_FMT_BGR24: planes_strip<CAIRO_FMT_BGR24>(src, sp, w, h, pitch, dst, sx, qy, m); break;
+    case CAIRO_FMT_I420:
+      if (col == 0)
+        planes_strip<CAIRO_FMT_I420>(src, sp, w, h, pitch, dst, sx, qy, m);
+      else if (col == 1)
+        planes_strip<CAIRO_FMT_I420, kColorDiagonal>(src, sp, w, h, pitch, dst, sx, qy, m);
+      else
+        planes_strip<CAIRO_FMT_I420, kColorFull>(src, sp, w, h, pitch, dst, sx, qy, m);
+      break;
+    default:
+      if (col == 0)
+        planes_strip<CAIRO_FMT_NV12>(src, sp, w, h, pitch, dst, sx, qy, m);
+      else if (col == 1)
+        planes_strip<CAIRO_FMT_NV12, kColorDiagonal>(src, sp, w, h, pitch, dst, sx, qy, m);
+      else
+        planes_strip<CAIRO_FMT_NV12, kColorFull>(src, sp, w, h, pitch, dst, sx, qy, m);
+      break;
   }
+}
+
+// The integer maps by direction and description index (kernels.h color_index):
+// k_ij = floor(2^14 c_ij + 1/2) of the real matrices of cairo_amd.h, derived in
+// exact rationals (tests/color_ref.py re-derives them from Kr and Kb, and
+// tests/test_color.py pins this table to that derivation).
+constexpr ColorMap kColorTable[2][kColorMaps] = {
+    {{16384, 0, 0, 16384, 0, 0, 16384, 0},                // in: FULL, BT601 (the identity)
+     {19077, 0, 0, 18651, 0, 0, 18651, 16},               //     LIMITED, BT601
+     {16384, 1664, 3213, 16218, -1813, -1187, 16112, 0},  //     FULL, BT709
+     {19077, 1895, 3657, 18462, -2064, -1351, 18342, 16}},  //   LIMITED, BT709
+    {{16384, 0, 0, 16384, 0, 0, 16384, 0},                  // out
+     {14071, 0, 0, 14392, 0, 0, 14392, 16},
+     {16384, -1936, -3485, 16689, 1878, 1230, 16799, 0},
+     {14071, -1663, -2993, 14660, 1650, 1080, 14757, 16}}};
+
+bool color_known(int range, int matrix) {
+  return (range == CAIRO_RANGE_FULL || range == CAIRO_RANGE_LIMITED) &&
+         (matrix == CAIRO_MATRIX_BT601 || matrix == CAIRO_MATRIX_BT709);
 }
 
 constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
@@ -294,14 +421,17 @@ dim3 strip_grid(int w, int h, int slices) {
 }  // namespace
 
 hipError_t launch_convert_fmt_batch(const ConvertFmtArgs& e, hipStream_t s) {
-  hipLaunchKernelGGL(k_convert_fmt_batch, strip_grid(e.c.w, e.c.h, e.c.nframes + 1), dim3(kFmtThreads), 0, s, e);
+  ConvertFmtArgs a = e;
+  for (int k = 0; k < kColorMaps; k++) a.map[k] = kColorTable[0][k];
+  hipLaunchKernelGGL(k_convert_fmt_batch, strip_grid(e.c.w, e.c.h, e.c.nframes + 1), dim3(kFmtThreads), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_planes_to_fmt(PlaneSet src, int plane_pitch, int w, int h, int fmt, uint32_t pitch, uint8_t* dst,
-                                hipStream_t s) {
+                                int col, hipStream_t s) {
+  if (col < 0 || col >= kColorMaps) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_planes_to_fmt, strip_grid(w, h, 1), dim3(kFmtThreads), 0, s, src, plane_pitch, w, h, fmt, pitch,
-                     dst);
+                     dst, col, kColorTable[1][col]);
   return hipGetLastError();
 }
 
@@ -325,14 +455,30 @@ int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint32_t pitch,
   return kSuccess;
 }
 
+int cairo_color_coefs(int dir, int range, int matrix, int32_t k[9], int32_t* offset) {
+  if (dir < 0 || dir > 1 || !color_known(range, matrix) || !k || !offset) return kInvalidArg;
+  const ColorMap& m = kColorTable[dir][color_index(range, matrix)];
+  const int32_t rows[9] = {m.k00, m.k01, m.k02, 0, m.k11, m.k12, 0, m.k21, m.k22};
+  for (int i = 0; i < 9; i++) k[i] = rows[i];
+  *offset = m.oy;
+  return kSuccess;
+}
+
 int cairo_kat_convert(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, uint8_t* frame, int16_t* y, int16_t* u,
                       int16_t* v, int device) {
+  return cairo_kat_convert_color(dir, fmt, CAIRO_RANGE_FULL, CAIRO_MATRIX_BT601, w, h, pitch, frame, y, u, v, device);
+}
+
+int cairo_kat_convert_color(int dir, int fmt, int range, int matrix, uint32_t w, uint32_t h, uint32_t pitch,
+                            uint8_t* frame, int16_t* y, int16_t* u, int16_t* v, int device) {
   uint64_t bytes = 0;
   uint32_t tight = 0;
   // (a grid's y extent is at most 65535 row pairs; column offsets are ints)
-  if (dir < 0 || dir > 1 || !frame || !y || !u || !v || w > (1u << 20) || h > 2 * 65535u ||
+  if (dir < 0 || dir > 1 || !frame || !y || !u || !v || w > (1u << 20) || h > 2 * 65535u || !color_known(range, matrix) ||
       cairo_frame_layout(fmt, w, h, pitch, &bytes, &tight) != kSuccess)
     return kInvalidArg;
+  const bool yuv = fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_NV12;
+  const int col = yuv ? color_index(range, matrix) : 0;  // an RGB frame has no description
   if (!pitch) pitch = tight;
   int r = fail(hipSetDevice(device), "hipSetDevice");
   if (r) return r;
@@ -350,6 +496,7 @@ int cairo_kat_convert(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, 
       a.c.in[0] = p;
       a.fmt[0] = (uint8_t)fmt;
       a.pitch[0] = pitch;
+      a.col[0] = (uint8_t)col;
       if ((r = fail(hipMemcpy(df, frame, bytes, hipMemcpyHostToDevice), "h2d")) ||
           (r = fail(launch_convert_fmt_batch(a, nullptr), "k_convert_fmt_batch")) ||
           (r = fail(hipDeviceSynchronize(), "sync")) ||
@@ -362,7 +509,7 @@ int cairo_kat_convert(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, 
           (r = fail(hipMemcpy(p.y, y, ny * 2, hipMemcpyHostToDevice), "h2d")) ||
           (r = fail(hipMemcpy(p.u, u, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
           (r = fail(hipMemcpy(p.v, v, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-          (r = fail(launch_planes_to_fmt(p, (int)w, (int)w, (int)h, fmt, pitch, df, nullptr), "k_planes_to_fmt")) ||
+          (r = fail(launch_planes_to_fmt(p, (int)w, (int)w, (int)h, fmt, pitch, df, col, nullptr), "k_planes_to_fmt")) ||
           (r = fail(hipDeviceSynchronize(), "sync")) ||
           (r = fail(hipMemcpy(frame, df, bytes, hipMemcpyDeviceToHost), "d2h")))
         goto done;

@@ -53,7 +53,11 @@ extern "C" {
  *   4  (unchanged) cairo_table_check and cairo_desc_check are added.  The
  *      drop-in decoder refuses with an error some tables it used to decode
  *      (see cairo_table_check); every stream the reference encoder writes
- *      decodes as before. */
+ *      decodes as before.
+ *   4  (unchanged) colour descriptions add entry points only:
+ *      cairo_color_coefs, cairo_ctx_set_input_color, cairo_ctx_set_output_color,
+ *      cairo_kat_convert_color, evx_encoder_set_input_color,
+ *      evx_decoder_set_output_color. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -70,11 +74,11 @@ typedef struct cairo_ctx cairo_ctx;
 #define CAIRO_FMT_NV12  3  /* Y: height rows of pitch bytes; then height/2 rows of pitch  */
                            /* bytes of interleaved U,V (U first). pitch >= width          */
 /* BGR24 is RGB24 with the first and third byte swapped: same arithmetic, same
- * bits.  I420 and NV12 carry the codec's own colour space, full-range BT.601
- * (JFIF): on input the internal planes are Y8 + 16, U8, V8 with no conversion;
- * on output Y8 = clamp(Y - 16), U8 = clamp(U), V8 = clamp(V), clamped to
- * 0..255.  Limited-range video (Y 16..235, chroma 16..240) must be expanded
- * to full range by the caller first: there is no range flag.
+ * bits.  I420 and NV12 carry, by default, the codec's own colour space,
+ * full-range BT.601 (JFIF): on input the internal planes are Y8 + 16, U8, V8
+ * with no conversion; on output Y8 = clamp(Y - 16), U8 = clamp(U),
+ * V8 = clamp(V), clamped to 0..255.  Limited-range and BT.709 frames are taken
+ * and written under a colour description (below).
  * Pixels outside width x height are never read; on output the bytes of a row
  * beyond the image (the pitch padding) are never written. */
 /* Buffer size and tight pitch of a frame (no device needed).
@@ -83,6 +87,74 @@ typedef struct cairo_ctx cairo_ctx;
  * NULL. */
 CAIRO_API int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint32_t pitch,
                                  uint64_t *bytes, uint32_t *tight_pitch);
+
+/* ---- colour descriptions ----------------------------------
+ * A colour description is a pair (range, matrix): */
+#define CAIRO_RANGE_FULL    0   /* Y, U, V 0..255 (today) */
+#define CAIRO_RANGE_LIMITED 1   /* Y 16..235, chroma 16..240 nominal */
+#define CAIRO_MATRIX_BT601  0   /* Kr = 0.299,  Kb = 0.114 (today) */
+#define CAIRO_MATRIX_BT709  1   /* Kr = 0.2126, Kb = 0.0722 */
+/* (FULL, BT601) is the codec's own space and the identity.  The description
+ * applies only to the 8-bit samples of I420 and NV12 frames.  RGB24 and BGR24
+ * frames are taken and returned exactly as today whatever the description is,
+ * so one launch and one ladder may mix them.
+ *
+ * Two maps are defined on the 8-bit sample triple:
+ *   dir 0: described YUV to the codec's full-range BT.601 (input).
+ *   dir 1: the codec's to described YUV (output).
+ * A luma sample at (x, y) uses the chroma sample at (x>>1, y>>1), as the
+ * codec's 4:2:0 does everywhere.  Chroma outputs never depend on luma.
+ *
+ * The real-valued matrix.  A(Kr, Kb), with Kg = 1 - Kr - Kb, is the RGB->YCbCr
+ * matrix with rows
+ *   [Kr, Kg, Kb]
+ *   [-Kr, -Kg, 1-Kb] / (2(1-Kb))
+ *   [1-Kr, -Kg, -Kb] / (2(1-Kr))
+ * Then C_in(BT709) = A(601) A(709)^-1 and C_out(BT709) = A(709) A(601)^-1; both
+ * have the shape [1 a b; 0 c d; 0 e f].  C(BT601) = I.  The range factors are
+ * sy = 255/219 and sc = 255/224 for LIMITED, and 1 for FULL.  On input, column
+ * 0 of C_in is multiplied by sy and columns 1 and 2 by sc, and oy = 16 is
+ * subtracted from Y first.  On output, row 0 of C_out is divided by sy and rows
+ * 1 and 2 by sc, and oy = 16 is added to Y.  (oy = 0 for FULL.)
+ *
+ * The integer coefficients.  k_ij = floor(2^14 c_ij + 1/2), computed in exact
+ * rationals.  With d0 = Y8 - oy on input (d0 = Y8 on output), d1 = U8 - 128
+ * and d2 = V8 - 128:
+ *   in : Y' = clamp((k00 d0 + k01 d1 + k02 d2 + 2^13) >> 14)
+ *   out: Y' = clamp((k00 d0 + k01 d1 + k02 d2 + (oy << 14) + 2^13) >> 14)
+ *        U' = clamp((k11 d1 + k12 d2 + (128 << 14) + 2^13) >> 14)
+ *        V' = clamp((k21 d1 + k22 d2 + (128 << 14) + 2^13) >> 14)
+ * >> is arithmetic, there is one rounding per sample, and everything fits
+ * int32.  The clamp is to 0..255.  Limited-range output is *not* clipped to
+ * 16..235/240, and input bytes outside the nominal range are legal and go
+ * through the same formula.
+ *
+ * How the maps compose with the existing paths.  Input: the internal planes
+ * are the existing rule (Y8' + 16, U8', V8') applied to the mapped samples.
+ * Output: the internal int16 samples are first clamped to 8 bits exactly as
+ * the identity output does (clamp(Y - 16), clamp(U), clamp(V)), then mapped.
+ * So for both directions the result equals the existing identity path composed
+ * with a pure byte-frame map.
+ *
+ * The error bound.  Each coefficient is off by at most 2^-15, and |d0| <= 255,
+ * |d1| and |d2| <= 128.  So every output is within 0.5 + 511/32768 of the
+ * real-arithmetic value.  The clamp is 1-Lipschitz, so the bound survives it. */
+/* The table the kernels use (host only, no device needed): k[9] row-major
+ * (k00 k01 k02 | 0 k11 k12 | 0 k21 k22) and *offset = oy for dir 0 / 1.
+ * EVX_ERROR_INVALID_ARGS for unknown values. */
+CAIRO_API int cairo_color_coefs(int dir, int range, int matrix, int32_t k[9], int32_t *offset);
+/* The description of the I420 / NV12 frames submitted from now on, through any
+ * of cairo_ctx_submit_fmt, cairo_ctx_submit_scaled and cairo_stream_submit_*.
+ * It is recorded per frame at submit, so it may change between submits with
+ * frames in flight, and one launch may mix descriptions.  A scaled frame is
+ * scaled first, on the samples as stored, then mapped: a scaled submit with a
+ * description gives the bits of submitting the scaled frame with it.  Survives
+ * cairo_ctx_reset; allowed for group members. */
+CAIRO_API int cairo_ctx_set_input_color(cairo_ctx *ctx, int range, int matrix);
+/* The description cairo_ctx_decode_frame_fmt and cairo_ctx_fetch_recon write
+ * I420 / NV12 frames in from now on.  cairo_ctx_decode_frame,
+ * cairo_ctx_fetch_recon_planes and the RGB formats are unchanged. */
+CAIRO_API int cairo_ctx_set_output_color(cairo_ctx *ctx, int range, int matrix);
 
 /* Outputs a context hands to the host entropy stage (cairo_ctx_set_outputs). */
 #define CAIRO_OUT_COEF 1 /* the output_cache planes (default)                   */
@@ -390,7 +462,9 @@ CAIRO_API int cairo_ctx_max_workgroups(const cairo_ctx *ctx);
  * over the nominal picture: width x height luma, (width/2) x (height/2)
  * chroma (index 0 Y, 1 U, 2 V); the padding up to 16 is excluded.  a is the
  * source (what an I420 submit carried, or the converted RGB), b the
- * reconstruction (what the decoder shows as I420).
+ * reconstruction (what the decoder shows as I420).  Under an input colour
+ * description a is the source after the map: what a full-range BT.601 I420
+ * submit of the mapped frame would carry.
  *   sse[p]      sum of (a - b)^2, exact.  PSNR = 10 log10(255^2 * samples[p] /
  *               sse[p]), infinite at sse 0; "all planes" uses the summed sse
  *               over the summed samples.
@@ -464,6 +538,12 @@ CAIRO_API int cairo_kat_transform(const int16_t *src, const int16_t *pred, const
  * bytes the kernel must not touch can be checked. */
 CAIRO_API int cairo_kat_convert(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, uint8_t *frame,
                                 int16_t *y, int16_t *u, int16_t *v, int device);
+/* The same under a colour description of the frame (dir 0: its input map,
+ * dir 1: its output map; ignored for the RGB formats).  cairo_kat_convert is
+ * (CAIRO_RANGE_FULL, CAIRO_MATRIX_BT601). */
+CAIRO_API int cairo_kat_convert_color(int dir, int fmt, int range, int matrix, uint32_t w, uint32_t h,
+                                      uint32_t pitch, uint8_t *frame, int16_t *y, int16_t *u, int16_t *v,
+                                      int device);
 
 /* ---- host entropy stage (serialize_slice, serialize.cpp:319-340) ---------
  * Appends the ABAC payload of one frame to out (LSB-first bit order) at bit
@@ -586,6 +666,9 @@ CAIRO_API int evx_encoder_set_device(void *enc, int device);  /* before first en
 /* The layout encode() reads its image in from now on (CAIRO_FMT_*, row pitch
  * in bytes, 0: tight); callable between frames.  peek() keeps writing RGB888. */
 CAIRO_API int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch);
+/* The colour description of the I420 / NV12 images encode() reads from now on
+ * (cairo_ctx_set_input_color); callable between frames. */
+CAIRO_API int evx_encoder_set_input_color(void *enc, int range, int matrix);
 /* CAIRO_METRIC_* for the frames encode() codes from now on (callable between
  * frames), and the metrics of the last encoded frame (EVX_ERROR_INVALID_ARGS
  * when it has none). */
@@ -604,6 +687,9 @@ CAIRO_API int evx_decoder_set_device(void *dec, int device); /* before first dec
 /* The layout decode() writes its frame in from now on (CAIRO_FMT_*, row pitch
  * in bytes, 0: tight; cairo_frame_layout bytes); callable between frames. */
 CAIRO_API int evx_decoder_set_output_format(void *dec, int fmt, uint32_t pitch);
+/* The colour description decode() writes I420 / NV12 frames in from now on
+ * (cairo_ctx_set_output_color); callable between frames. */
+CAIRO_API int evx_decoder_set_output_color(void *dec, int range, int matrix);
 
 /* bit_stream (reference bitstream.h:43-92) */
 CAIRO_API void *evx_bitstream_create(uint32_t size_in_bits);

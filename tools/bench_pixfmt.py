@@ -10,6 +10,12 @@ tests/test_pixfmt.py), then RGB24 and NV12 once more from pinned host memory
 (the PCIe-inclusive rate).  After timing, each format's block tables of the
 first `--check-frames` frames are compared with the RGB24 run's.
 
+Colour descriptions: the resident NV12 leg runs a second time
+("nv12_repeat"), so that the identity leg's own run-to-run spread in this
+process is known, and then once more with the same bytes *interpreted* as
+LIMITED / BT709 ("nv12_limited_bt709": the full colour map in the convert; its
+tables are another picture's, so they are not compared).
+
 Prints one JSON line.  The resident pool is `--pool` distinct frames, cycled,
 so a rate here is not bench.py's headline (whose frames are all distinct): the
 figures are for comparing the formats with each other.
@@ -81,8 +87,10 @@ def run(ctx, frame_of, first, count, q, on_device, fmt, log=None, tables=None):
         retire()
 
 
-def leg(cairo_amd, w, h, ring, q, batch, warm, timed, frame_of, on_device, fmt, check):
+def leg(cairo_amd, w, h, ring, q, batch, warm, timed, frame_of, on_device, fmt, check, color=None):
     ctx = cairo_amd.Context(w, h, ring)
+    if color is not None:
+        ctx.set_input_color(*color)
     ctx.set_batch(batch)
     ctx.set_outputs(cairo_amd.OUT_FEED)
     run(ctx, frame_of, 0, warm, q, on_device, fmt)
@@ -113,6 +121,8 @@ def main():
     p.add_argument("--pool", type=int, default=96, help="distinct resident frames per format, cycled")
     p.add_argument("--host-steps", type=int, default=12, help="timed launches of the host-fed legs (0: skip)")
     p.add_argument("--check-frames", type=int, default=48)
+    p.add_argument("--no-color", dest="color", action="store_false",
+                   help="skip the NV12 repeat and the NV12 LIMITED / BT709 legs")
     a = p.parse_args()
     import torch  # device and pinned memory only; before the library starts HIP
 
@@ -148,6 +158,24 @@ def main():
         else:
             res["tables_equal_rgb24"][NAMES[fmt]] = len(tables) == len(ref_tables) and all(
                 np.array_equal(x, y) for x, y in zip(tables, ref_tables))
+        if fmt == cairo_amd.FMT_NV12 and a.color:
+            frame_of = lambda f: base + (f % pool_n) * nb  # noqa: E731
+            rep, tables = leg(cairo_amd, w, h, ring, q, batch, warm, timed, frame_of, True, fmt, a.check_frames)
+            rep["source_bytes_per_frame"] = nb
+            res["resident"]["nv12_repeat"] = rep
+            res["tables_equal_rgb24"]["nv12_repeat"] = len(tables) == len(ref_tables) and all(
+                np.array_equal(x, y) for x, y in zip(tables, ref_tables))
+            col, _ = leg(cairo_amd, w, h, ring, q, batch, warm, timed, frame_of, True, fmt, 0,
+                         color=(cairo_amd.RANGE_LIMITED, cairo_amd.MATRIX_BT709))
+            col["source_bytes_per_frame"] = nb
+            res["resident"]["nv12_limited_bt709"] = col
+            lo, hi = sorted((out["value"], rep["value"]))
+            res["color"] = {"identity_runs": [out["value"], rep["value"]], "identity_spread_pct":
+                            round(100 * (hi - lo) / lo, 3), "limited_bt709": col["value"],
+                            "inside_identity_spread": lo <= col["value"] <= hi,
+                            "vs_identity_mean_pct": round(100 * (2 * col["value"] / (lo + hi) - 1), 3)}
+            print(f"[bench_pixfmt] nv12_repeat: {rep}\n[bench_pixfmt] nv12_limited_bt709: {col}", file=sys.stderr,
+                  flush=True)
         del dev
         torch.cuda.empty_cache()
         print(f"[bench_pixfmt] {NAMES[fmt]}: {out}", file=sys.stderr, flush=True)
