@@ -19,6 +19,7 @@
 // then replay the reference's sequential, tie-sensitive acceptance in the
 // reference's scan order (j outer, i inner) with wave-uniform scalars.
 #include "kernels.h"
+#include "search_geometry.h"
 
 namespace cairo {
 
@@ -203,8 +204,12 @@ __device__ __forceinline__ void acct_start(uint64_t* acct, int k, uint64_t v) {
 #endif
 #if CAIRO_ASM_MARKS
 #define ASM_MARK(s) asm volatile("; cairo-mark " s)
+#define ASM_PIN(v) asm volatile("" : "+v"(v))  // v is computed before, and used after, this point
+#define ASM_USE(v) asm volatile("" ::"v"(v))   // v is computed before this point
 #else
 #define ASM_MARK(s) ((void)0)
+#define ASM_PIN(v) ((void)0)
+#define ASM_USE(v) ((void)0)
 #endif
 
 // Deblock progress words (kernels.h FrameArgs::progress): tag a column count
@@ -697,6 +702,13 @@ __device__ __forceinline__ uint32_t lerp_quarter_bb3(uint32_t a3, uint32_t b) { 
   return (t + 1 + ((t >> 17) & 1)) >> 2;
 }
 __device__ __forceinline__ uint32_t lerp_quarter_bb(uint32_t a, uint32_t b) { return lerp_quarter_bb3(3 * a, b); }
+// Both of them with q (0 half, 1 quarter) as data: for a wave-uniform q the
+// four instructions take their weight, bit and shift from scalar registers,
+// and no branch is needed to choose between the two.
+__device__ __forceinline__ uint32_t lerp_q_bb(uint32_t a, uint32_t b, int q) {
+  const uint32_t t = a * (uint32_t)(1 + 2 * q) + b;  // a'+b' or 3a'+b'
+  return (t + (uint32_t)q + ((t >> (16 + q)) & 1)) >> (1 + q);
+}
 __device__ __forceinline__ uint32_t absdiff_b(uint32_t x, uint32_t y) {  // biased values
   return __builtin_amdgcn_sad_u16(x, y, 0);
 }
@@ -867,6 +879,9 @@ __device__ __forceinline__ bool select_int2(Sel& s, bool two, bool valid, int cx
   const int c = lane & 15;
   const bool live = lane < (two ? 32 : 16) && valid;
   const int ssd = (cx - px) * (cx - px) + (cy - py) * (cy - py);
+  ASM_USE(ssd);
+  ASM_MARK("replay_coords end");
+  ASM_MARK("replay_select begin");
   const uint32_t fm2 = (uint32_t)__ballot(live && mad < thr);
   const uint32_t fm0 = fm2 & 0xFFFFu, fm1 = fm2 >> 16;
   const bool copy = s.mad < thr;
@@ -2109,7 +2124,7 @@ struct alignas(16) RowLds {
   RowWindow win;
   alignas(16) int16_t src[2][384];  // source macroblocks bx, bx+1 (by bx & 1), group_source layout
   int16_t bufA[kMBElems], bufB[kMBElems];  // per-block transform scratch, block-major
-  int32_t cand[2][16][2];                  // double-buffered candidate (sad, mad)
+  alignas(16) int32_t cand[2][16][4];      // double-buffered candidate (sad, mad, packed cx | cy; one spare)
   int32_t red[12];
 };
 
@@ -2164,6 +2179,8 @@ __device__ __forceinline__ void cand_row(const RowWindow& w, int oy, int cx, int
   const int c = cx & 127, sh = (c & 1) * 2;
   const uint32_t* row = (const uint32_t*)&w.y[(cy + i - oy) * kCwLP] + (c >> 1);
   uint32_t d[9];
+  ASM_MARK("eval_coords end");
+  ASM_MARK("eval_sad begin");
 #pragma unroll
   for (int k = 0; k < 9; k++) d[k] = row[k];
   uint32_t sm = 0;
@@ -2193,15 +2210,15 @@ __device__ __forceinline__ void cand_row(const RowWindow& w, int oy, int cx, int
 // On the biased halves directly (lerp_half_bb).
 __device__ __forceinline__ uint32_t lerp_pair(uint32_t pa, uint32_t pb, int q) {
   const uint32_t a0 = pa & 0xFFFFu, b0 = pb & 0xFFFFu, a1 = pa >> 16, b1 = pb >> 16;
-  const uint32_t l0 = q ? lerp_quarter_bb(a0, b0) : lerp_half_bb(a0, b0);
-  const uint32_t l1 = q ? lerp_quarter_bb(a1, b1) : lerp_half_bb(a1, b1);
-  return l0 | (l1 << 16);
+  return lerp_q_bb(a0, b0, q) | (lerp_q_bb(a1, b1, q) << 16);
 }
 
 // Sub-pel candidate: lerp of the best block (bx, by) toward neighbour (tx, ty),
 // read like cand_row (aligned dwords of the circular window and its
 // duplicated tail, realigned by v_alignbyte_b32); the lerped pairs are
-// re-biased so that SAD and MAD use the same packed u16 ops.
+// re-biased so that SAD and MAD use the same packed u16 ops.  q (half or
+// quarter step) is the same in a whole wave and only data to the lerp
+// (lerp_q_bb), so the body is straight-line.
 __device__ __forceinline__ void subpel_row(const RowWindow& w, int oy, int bx, int by, int tx,
                                            int ty, int q, int i, const SrcRow& s, int thr, int& sad,
                                            int& mad) {
@@ -2253,8 +2270,7 @@ __device__ __forceinline__ void subpel_row(const RowWindow& w, int oy, int bx, i
 }
 
 __device__ __forceinline__ bool intra_valid(int cx, int cy, int px, int py, int wa, int ha) {
-  if (cy > py - kMB && cx > px - kMB) return false;  // not yet coded (motion.cpp:239-243)
-  return in_frame(cx, cy, wa, ha);
+  return sg::intra_valid(cx, cy, px, py, wa, ha);  // in the frame and already coded (motion.cpp:239-243)
 }
 
 // Pixel (ex, ey) of plane pl (0 Y, 1 U, 2 V) from the window.
@@ -2552,18 +2568,30 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       if (!kDecode) {
         // ---- intra search (calculate_intra_prediction, motion.cpp:354-419) ----
         Sel sel;
+        ASM_MARK("src_sum begin");
         {
-          int sm = 0;
+          // compute_block_sad(src): |b - 0x8000| = |v| for a biased b = v + 0x8000,
+          // so the packed SAD against the bias; every group holds the total
   #pragma unroll
-          for (int k = 0; k < 16; k++) sm += abs(src_px(s.y, k));
-          sel.sad = uni(row16_sum(sm));  // compute_block_sad(src): every group holds the total
+          for (int k = 0; k < 8; k++) ASM_PIN(s.y[k]);
+          uint32_t sm = 0;
+  #pragma unroll
+          for (int k = 0; k < 8; k++) sm = __builtin_amdgcn_sad_u16(s.y[k], 0x80008000u, sm);
+          int tot = row16_sum((int)sm);
+          ASM_PIN(tot);
+          sel.sad = uni(tot);
         }
+        ASM_MARK("src_sum end");
         sel.bx = px;
         sel.by = py;
         sel.mad = INT32_MAX;
         sel.ssd = INT32_MAX;
         sel.sp_idx = sel.sp_amt = sel.sp_en = 0;
         int buf = 0;
+        // the unit offsets of this lane group's slot in the search's patterns
+        // (search_geometry.h): the same for every macroblock, but a few
+        // instructions here cost less than a register kept live across the row
+        const uint32_t units = sg::group_units(fresh(grp));
         uint64_t t_ev = 0, t_ba = 0, t_se = 0;  // (CAIRO_ACCT builds: the stages' phases)
         int passes = 0;  // (CAIRO_ACCT builds: evaluation passes of this macroblock)
         // Evaluation passes.  Stage 0 is a pass of its own:
@@ -2578,42 +2606,45 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         // the same in every wave, so is the decision.
   #pragma unroll 1
         for (int stage = 0; stage < ((CAIRO_ATTR_SKIP & 16) ? 0 : 5);) {
-          const int step = stage == 0 ? kRadius : (kRadius >> stage);
-          const int jlo = stage == 0 ? -2 * kRadius : -step;
-          const int n0 = stage == 0 ? 9 : 8;              // candidates of this stage
+          ASM_MARK("pass_head begin");
           const bool spec = stage >= 1 && stage < 4;      // the second half speculates stage + 1
           const int bx0 = sel.bx, by0 = sel.by;
           const uint64_t ts0 = acct_now();
+          ASM_MARK("pass_head end");
+          ASM_MARK("eval_coords begin");
           {
-            const bool second = stage >= 1 && grp >= 8;
-            const int c = second ? grp - 8 : grp;
-            const int k9 = stage == 0 || c < 4 ? c : c + 1;  // skip the centre of the 3x3
-            const int st = second ? step >> 1 : step;
-            if (second ? spec : grp < n0) {
-              const int cx = bx0 - st + (k9 % 3) * st, cy = by0 + (second ? -st : jlo) + (k9 / 3) * st;
+            // the group's slot is fixed (units); its step is the same in a
+            // whole wave (waves 2 and 3 are the speculated half)
+            static_assert(kRadius == 1 << sg::kRadiusLog2, "search_geometry.h's steps");
+            const int sh = uni(sg::group_shift(grp, stage));
+            if (sg::group_active(grp, stage)) {
+              int cx, cy;
+              sg::candidate(units, stage, sh, bx0, by0, cx, cy);
               const bool ok = intra_valid(cx, cy, px, py, vs.wa, vs.ha);
               int sad, mad;
               cand_row(L.win, oy, cx, ok ? cy : py - 48, gi, s, thr, sad, mad);
-              if (gi == 0) {
+              if (gi == 0) {  // (sad, mad) and, for the replay, where the candidate is
                 L.cand[buf][grp][0] = ok ? sad : -1;
                 L.cand[buf][grp][1] = mad;
+                L.cand[buf][grp][2] = (int32_t)sg::pack_xy(cx, cy);
               }
             }
           }
+          ASM_MARK("eval_sad end");
           const uint64_t ts1 = acct_now();
           __syncthreads();
           const uint64_t ts2 = acct_now();
+          ASM_MARK("replay_coords begin");
           {
             // lanes 0..15: this stage's entries; lanes 16..23: entries 8..15, stage + 1 if the centre stays
-            const int c = lane & 15;
-            const bool row1 = (lane & 16) != 0;
-            const int e = row1 ? 8 + (c & 7) : c;
-            const int vs = L.cand[buf][e][0], vm = L.cand[buf][e][1];
-            const int k9 = stage == 0 || c < 4 ? c : c + 1;
-            const int st = row1 ? step >> 1 : step;
-            const int cx = bx0 - st + (k9 % 3) * st, cy = by0 + (row1 ? -st : jlo) + (k9 / 3) * st;
-            stage += select_int2(sel, spec, c < (row1 ? 8 : n0) && vs >= 0, cx, cy, vs, vm, px, py, thr, lane) ? 2 : 1;
+            // (the entry's coordinates as its group stored them)
+            const int32_t* ce = L.cand[buf][sg::replay_entry(lane)];
+            const int vs = ce[0], vm = ce[1];
+            const uint32_t xy = (uint32_t)ce[2];
+            stage += select_int2(sel, spec, sg::replay_slot(lane, stage) && vs >= 0, sg::unpack_x(xy), sg::unpack_y(xy),
+                                 vs, vm, px, py, thr, lane) ? 2 : 1;
           }
+          ASM_MARK("replay_select end");
           buf ^= 1;
           if (CAIRO_ACCT) {
             const uint64_t ts3 = uni((int)sel.bx) == -99999 ? 0 : acct_now();  // after the replay's result
@@ -2630,12 +2661,13 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         }
         stamp(*ap, mb, 3);
         if (!(CAIRO_ATTR_SKIP & 16)) {  // sub-pel (perform_intra_subpixel_motion_search, motion.cpp:277-317)
+          ASM_MARK("subpel begin");
           const int bx0 = sel.bx, by0 = sel.by;
           // candidate c = 2 nn + q; q is wave-uniform (waves 0 and 2 the half
           // steps, 1 and 3 the quarter steps), so a wave runs one lerp, not both
-          const int q = (grp >> 2) & 1, nn = (grp & 3) | ((grp >> 3) << 2), c = 2 * nn + q;
-          const int k9 = nn < 4 ? nn : nn + 1;  // skip the centre of the 3x3
-          const int tx = bx0 + k9 % 3 - 1, ty = by0 + k9 / 3 - 1;
+          const int q = sg::subpel_q(grp), nn = sg::subpel_neighbour(grp), c = 2 * nn + q;
+          const int k9 = sg::skip_centre(nn);  // skip the centre of the 3x3
+          const int tx = bx0 + sg::unit_x(k9), ty = by0 + sg::unit_y(k9);
           const bool ok = intra_valid(tx, ty, px, py, vs.wa, vs.ha);
           int sad, mad;
           const uint64_t ts0 = acct_now();
@@ -2656,6 +2688,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
             acct_add(ap->acct, Acct::kSubBarrier, ts2 - ts1);
             acct_add(ap->acct, Acct::kSubSelect, ts3 - ts2);
           }
+          ASM_MARK("subpel end");
         }
         stamp(*ap, mb, 4);
         acct_add(ap->acct, Acct::kCoderSearch, acct_now() - tacc);
