@@ -262,6 +262,88 @@ def make_sequence(width: int, height: int, ring: int, frames: int, seed: int):
 
 
 # ---------------------------------------------------------------------------
+# Sequences for the deblock: tables and coefficients whose planes before the
+# deblock are flat 8x8 blocks a small step apart, so that the alpha/beta test
+# passes on a large share of the edges and filtered lines read what earlier
+# lines wrote (tests/deblock_ref.py classifies them, tests/test_deblock.py
+# asserts the shares).
+# ---------------------------------------------------------------------------
+
+DEBLOCK_Q = (8, 31)  # alpha and beta are 0 below q_index 7 and 8
+DEBLOCK_TYPES, DEBLOCK_TYPE_P = (1, 0, 4, 6), (0.3, 0.3, 0.3, 0.1)
+# A chain: a type-1 macroblock with a flat DC and CHAIN-1 type-3 macroblocks to
+# its right, each predicting from its left neighbour (vector (-16, 0)) and
+# adding the same flat step, all at q_index CHAIN_Q.  A flat block from one DC
+# reaches +-4048 at most (two passes of 45/128 over a dequantized 32767), so
+# the fifth macroblock holds +-20240.  Two chains of opposite sign in
+# adjacent rows put a step of 40480 across the H edge between their last
+# macroblocks: |p0 - q0| narrowed to int16 is negative, below alpha, and the
+# filter fires across it, which it would not without the narrowing.
+CHAIN, CHAIN_Q = 5, 16
+CHAIN_DC_INTRA = 32767 // 24  # luma DC scale q + 8 at q = 16 (quantize.cpp:37-55); the chroma scale is smaller
+CHAIN_DC_INTER = 32767 // (2 * CHAIN_Q)  # 2 v qm q / 16 with qm = 16 (quantize.cpp:232-243)
+
+
+def make_deblock_frame(wmb: int, hmb: int, ring: int, index: int, seed: int):
+    """(table, (y, u, v)) of frame `index`."""
+    rng = np.random.default_rng([seed, index, wmb, hmb, ring, 7])
+    nmb = wmb * hmb
+    table = np.zeros(nmb, BLOCK_DESC)
+    y = np.zeros((hmb * 16, wmb * 16), np.int16)
+    u = np.zeros((hmb * 8, wmb * 8), np.int16)
+    v = np.zeros((hmb * 8, wmb * 8), np.int16)
+
+    def blocks(bx, by):
+        out = [y[by * 16 + j:by * 16 + j + 8, bx * 16 + i:bx * 16 + i + 8] for j in (0, 8) for i in (0, 8)]
+        return out + [u[by * 8:by * 8 + 8, bx * 8:bx * 8 + 8], v[by * 8:by * 8 + 8, bx * 8:bx * 8 + 8]]
+
+    chained = set()
+    # every fourth frame, the last of a four-frame sequence: the frames after a chain inherit its +-20240 levels,
+    # whose edges no longer fire, which costs a frame of 39 macroblocks a quarter of its lines
+    if index % 4 == 3 and wmb >= CHAIN and hmb >= 2:
+        bx0, by0 = int(rng.integers(0, wmb - CHAIN + 1)), int(rng.integers(0, hmb - 1))
+        for row, sign in ((by0, 1), (by0 + 1, -1)):
+            for k in range(CHAIN):
+                d = table[row * wmb + bx0 + k]
+                d["block_type"], d["q_index"] = (1, CHAIN_Q) if k == 0 else (3, CHAIN_Q)
+                d["motion_x"] = 0 if k == 0 else -16
+                for b in blocks(bx0 + k, row):
+                    b[0, 0] = sign * (CHAIN_DC_INTRA if k == 0 else CHAIN_DC_INTER)
+                chained.add(row * wmb + bx0 + k)
+
+    for i in range(nmb):
+        if i in chained:
+            continue
+        bx, by = i % wmb, i // wmb
+        t = 1 if index == 0 else int(rng.choice(DEBLOCK_TYPES, p=DEBLOCK_TYPE_P))
+        d = table[i]
+        d["block_type"], d["prediction_target"] = t, 1
+        d["q_index"] = int(rng.integers(DEBLOCK_Q[0], DEBLOCK_Q[1] + 1))
+        while t & MOTION:  # a short vector that stays in the frame, with or without a sub-pel neighbour
+            d["motion_x"], d["motion_y"] = int(rng.integers(-4, 5)), int(rng.integers(-4, 5))
+            d["sp_pred"], d["sp_amount"] = int(rng.integers(0, 2)), int(rng.integers(0, 2))
+            d["sp_index"] = int(rng.integers(0, 8))
+            if _alone(d, bx, by, wmb, hmb, ring):
+                break
+        for b in blocks(bx, by):  # copies get coefficients too: they must be ignored
+            b[0, 0] = (30 if t == 1 else 0) + int(rng.integers(-1, 2))
+            if rng.random() < 0.3:
+                b[0, 1], b[1, 0] = int(rng.integers(-1, 2)), int(rng.integers(-1, 2))
+    assert cairo_amd.table_check(table, wmb, hmb, ring)
+    return table, (y, u, v)
+
+
+def make_deblock_sequence(width: int, height: int, ring: int, frames: int, seed: int):
+    """[(table, (y, u, v))] for frames 0..frames-1: frame 0 is type 1
+    throughout, later frames mix types 1, 0, 4 and 6 on target 1; q_index is
+    uniform in DEBLOCK_Q; every 8x8 block holds a DC a step of -1, 0 or 1 from
+    its type's level and now and then the two lowest AC terms; frames 3, 7, ...
+    carry a pair of chains (above) where the frame has room."""
+    wmb, hmb = (width + 15) // 16, (height + 15) // 16
+    return [make_deblock_frame(wmb, hmb, ring, t, seed) for t in range(frames)]
+
+
+# ---------------------------------------------------------------------------
 # Which directed classes a desc meets, read off the desc alone (whoever placed it).
 # ---------------------------------------------------------------------------
 
