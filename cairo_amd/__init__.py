@@ -112,6 +112,16 @@ def lib() -> ctypes.CDLL:
         "cairo_ctx_submit_scaled": (I, [P, P, I, U, P, U, U, U, ctypes.POINTER(I)]),
         "cairo_stream_submit_scaled": (I, [P, P, I, U, P, U, U, U, ctypes.POINTER(I)]),
         "cairo_kat_scale": (I, [I, U, P, P, U, U, P, I]),
+        "cairo_tensor_size": (I, []),
+        "cairo_tensor_check": (I, [P, P, U, U, ctypes.POINTER(ctypes.c_uint64)]),
+        "cairo_tensor_host": (I, [I, P, U, U, P, P]),
+        "cairo_kat_tensor": (I, [I, P, U, U, P, ctypes.c_uint64, P, I]),
+        "cairo_ctx_submit_tensor": (I, [P, P, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_stream_submit_tensor": (I, [P, P, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_ctx_decode_frame_tensor": (I, [P, P, P, U, P, P]),
+        "cairo_ctx_fetch_recon_tensor": (I, [P, I, P, P]),
+        "evx_encoder_set_input_tensor": (I, [P, P]),
+        "evx_decoder_set_output_tensor": (I, [P, P]),
         "cairo_frame_metrics_size": (I, []),
         "cairo_ctx_set_metrics": (I, [P, I]),
         "cairo_ctx_frame_metrics": (I, [P, I, P]),
@@ -361,6 +371,161 @@ def _scaled_source_ptr(frame, on_device: bool, fmt: int, src_size, pitch: int) -
     return frame.ctypes.data
 
 
+# Tensor frames (include/cairo_amd.h cairo_tensor, CAIRO_DT_*)
+DT_U8, DT_F16, DT_BF16, DT_F32 = range(4)
+DT_SIZE = {DT_U8: 1, DT_F16: 2, DT_BF16: 2, DT_F32: 4}
+KAT_TENSOR_GUARD = 64  # CAIRO_KAT_TENSOR_GUARD
+_DT_NAMES = {"uint8": DT_U8, "float16": DT_F16, "half": DT_F16, "bfloat16": DT_BF16, "float32": DT_F32,
+             "float": DT_F32}
+
+
+class _Tensor(ctypes.Structure):
+    """cairo_tensor (include/cairo_amd.h)."""
+    _fields_ = [
+        ("dtype", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32),
+        ("stride", ctypes.c_int64 * 3),
+        ("mul", ctypes.c_float * 3),
+        ("add", ctypes.c_float * 3),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
+@dataclass
+class TensorDesc:
+    """A tensor frame: the address of element (0, 0, 0), its cairo_tensor (c,
+    a ctypes structure), the frame size where the shape gave one, and the
+    object that owns the memory."""
+    ptr: int
+    c: _Tensor
+    width: int | None = None
+    height: int | None = None
+    owner: object = None
+
+
+def _three(v, what: str):
+    a = np.asarray(v, np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 3)
+    if a.size != 3:
+        raise ValueError(f"{what} is a number or three numbers (R, G, B)")
+    return a
+
+
+def tensor_desc(t, mul=None, add=None, value_range=(0.0, 1.0), output: bool = False) -> TensorDesc:
+    """Describe a tensor frame.  t is any object with data_ptr(), dtype, shape,
+    stride() and device (a torch tensor; this package does not import torch),
+    of shape (3, H, W) or (H, W, C >= 3) with positive strides: a frame of an
+    NCHW batch, a channels_last view, a crop and the RGB channels of an RGBA
+    tensor all qualify.  A numpy array is taken the same way (host tensors, for
+    tensor_host and kat_tensor), and so is a plain (ptr, dtype, strides) with
+    dtype a DT_* value or a name and strides = (channel, row, column) in
+    elements.  The dtype is read from its name: uint8, float16, bfloat16 or
+    float32.
+
+    The map (include/cairo_amd.h): input s = clamp(rint(fmaf(x, mul, add))),
+    output x = fmaf(s, mul, add).  mul / add: numbers or per-channel triples;
+    left out, they come from value_range = (lo, hi), the values 0 and 255 stand
+    for: for an input (output=False) mul = 255 / (hi - lo), add = -lo * mul; for
+    an output mul = (hi - lo) / 255, add = lo -- computed in double, rounded
+    once to float32."""
+    if isinstance(t, TensorDesc):
+        return t
+    width = height = None
+    if isinstance(t, tuple):
+        ptr, dt, strides = t
+        owner = None
+    else:
+        shape = tuple(int(x) for x in t.shape)
+        if isinstance(t, np.ndarray):
+            ptr, st = t.ctypes.data, tuple(s // t.itemsize for s in t.strides)
+        else:
+            ptr, st = int(t.data_ptr()), tuple(int(s) for s in t.stride())
+        dt = str(t.dtype)
+        if len(shape) != 3:
+            raise ValueError(f"a tensor frame has shape (3, H, W) or (H, W, C >= 3), got {shape}")
+        if shape[0] == 3:
+            strides, height, width = (st[0], st[1], st[2]), shape[1], shape[2]
+        elif shape[2] >= 3:
+            strides, height, width = (st[2], st[0], st[1]), shape[0], shape[1]
+        else:
+            raise ValueError(f"a tensor frame has shape (3, H, W) or (H, W, C >= 3), got {shape}")
+        owner = t
+    if isinstance(dt, str):
+        name = dt.rsplit(".", 1)[-1]
+        if name not in _DT_NAMES:
+            raise ValueError(f"tensor frames are uint8, float16, bfloat16 or float32, got {dt}")
+        dt = _DT_NAMES[name]
+    if mul is None and add is None:
+        lo, hi = float(value_range[0]), float(value_range[1])
+        if not hi > lo:
+            raise ValueError(f"value_range is (lo, hi) with hi > lo, got {value_range}")
+        if output:
+            mul, add = (hi - lo) / 255.0, lo
+        else:
+            mul = 255.0 / (hi - lo)
+            add = -lo * mul
+    c = _Tensor()
+    c.dtype = int(dt)
+    c.stride[:] = [int(s) for s in strides]
+    c.mul[:] = [float(np.float32(x)) for x in _three(1.0 if mul is None else mul, "mul")]
+    c.add[:] = [float(np.float32(x)) for x in _three(0.0 if add is None else add, "add")]
+    return TensorDesc(int(ptr), c, width, height, owner)
+
+
+def tensor_check(desc: TensorDesc, w: int, h: int, ptr: int | None = None):
+    """-> the span in bytes of a w x h tensor frame, or None when the
+    descriptor is not valid for it (cairo_tensor_check; ptr: another base
+    address, of which only the alignment counts).  No device needed."""
+    span = ctypes.c_uint64()
+    base = desc.ptr if ptr is None else ptr
+    if lib().cairo_tensor_check(ctypes.byref(desc.c), base, w, h, ctypes.byref(span)):
+        return None
+    return span.value
+
+
+def tensor_host(direction: int, desc: TensorDesc, w: int, h: int, rgb: np.ndarray) -> None:
+    """The tensor map as host loops (cairo_tensor_host) between the host
+    tensor at desc.ptr and the tight RGB24 frame rgb (3 * w * h uint8):
+    direction 0 writes rgb, 1 writes the tensor's covered elements."""
+    if not isinstance(rgb, np.ndarray) or rgb.dtype != np.uint8 or rgb.size != 3 * w * h or \
+            not rgb.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"rgb must be a C-contiguous uint8 array of {3 * w * h} bytes")
+    _ck(lib().cairo_tensor_host(direction, ctypes.byref(desc.c), w, h, desc.ptr, _ptr(rgb)), "cairo_tensor_host")
+
+
+def kat_tensor(direction: int, desc: TensorDesc, w: int, h: int, nbytes: int, rgb: np.ndarray,
+               device: int = 0) -> None:
+    """The tensor kernels on host buffers, without a context
+    (cairo_kat_tensor): the nbytes of host memory at desc.ptr (the span and
+    any guard) and rgb (3 * w * h + KAT_TENSOR_GUARD uint8) are uploaded, the
+    kernel of the direction runs, and both are read back in place.  The device
+    copy keeps desc.ptr modulo 16."""
+    if not isinstance(rgb, np.ndarray) or rgb.dtype != np.uint8 or rgb.size != 3 * w * h + KAT_TENSOR_GUARD or \
+            not rgb.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"rgb must be a C-contiguous uint8 array of {3 * w * h + KAT_TENSOR_GUARD} bytes")
+    _ck(lib().cairo_kat_tensor(direction, ctypes.byref(desc.c), w, h, desc.ptr, nbytes, _ptr(rgb), device),
+        "cairo_kat_tensor")
+
+
+def _frame_tensor(t, width: int, height: int, output: bool, kw: dict) -> TensorDesc:
+    """The descriptor of a tensor handed to a context of width x height."""
+    d = tensor_desc(t, output=output, **kw)
+    if d.width is not None and (d.width, d.height) != (width, height):
+        raise ValueError(f"the tensor is a {d.width}x{d.height} frame, the context's are {width}x{height}")
+    return d
+
+
+def _sync_producer(t) -> None:
+    """Order a torch tensor's producer before a submit: synchronise the
+    current stream of its device.  Only when the caller already imported
+    torch; the C ABI leaves the ordering to the caller."""
+    import sys
+    torch = sys.modules.get("torch")
+    if torch is not None and getattr(t, "is_cuda", False):
+        torch.cuda.current_stream(t.device).synchronize()
+
+
 def make_band4(w: int, h: int, t: int, seed: int = 1234) -> np.ndarray:
     """band4 synthetic RGB888 frame, shape (h, w, 3)."""
     out = np.empty((h, w, 3), np.uint8)
@@ -510,6 +675,23 @@ class Context:
             self._keep[t.value] = rgb
         return t.value
 
+    def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, **desc) -> int:
+        """Submit a tensor frame in device memory (cairo_ctx_submit_tensor): t
+        and the keywords mul, add, value_range are tensor_desc's (or t is a
+        TensorDesc).  Produces the bits of submitting the RGB24 frame the input
+        map gives.  t is kept alive until the ticket's wait and must not
+        change before it.  sync: synchronise the producer's current stream
+        first when torch is already imported (the C ABI leaves that ordering to
+        the caller)."""
+        d = _frame_tensor(t, self.width, self.height, False, desc)
+        if sync:
+            _sync_producer(d.owner)
+        tk = ctypes.c_int()
+        _ck(self.L.cairo_ctx_submit_tensor(self.h, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
+                                           ctypes.byref(tk)), "cairo_ctx_submit_tensor")
+        self._keep[tk.value] = d
+        return tk.value
+
     def wait(self, ticket: int, copy: bool = True) -> FrameOutputs:
         r = _FrameResult()
         st = self.L.cairo_ctx_wait(self.h, ticket, ctypes.byref(r))
@@ -636,6 +818,15 @@ class Context:
         _ck(self.L.cairo_ctx_fetch_recon(self.h, ticket, fmt, pitch, _ptr(out)), "cairo_ctx_fetch_recon")
         return out
 
+    def fetch_recon_tensor(self, ticket: int, t, **desc):
+        """The same frame as RGB through the output map into the device tensor
+        t (cairo_ctx_fetch_recon_tensor; t and the keywords as tensor_desc's
+        with output=True) -> t.  Synchronous; no copy to the host."""
+        d = _frame_tensor(t, self.width, self.height, True, desc)
+        _ck(self.L.cairo_ctx_fetch_recon_tensor(self.h, ticket, d.ptr, ctypes.byref(d.c)),
+            "cairo_ctx_fetch_recon_tensor")
+        return t
+
     def release(self, ticket: int) -> None:
         _ck(self.L.cairo_ctx_release(self.h, ticket), "cairo_ctx_release")
 
@@ -659,6 +850,20 @@ class Context:
         rgb = np.empty((self.height, self.width, 3), np.uint8)
         _ck(self.L.cairo_ctx_decode_frame(self.h, _ptr(t), _ptr(coef), index, _ptr(rgb)), "cairo_ctx_decode_frame")
         return rgb
+
+    def decode_frame_tensor(self, table: np.ndarray, planes, index: int, t, **desc):
+        """decode_frame written through the output map into the device tensor t
+        (cairo_ctx_decode_frame_tensor; t and the keywords as tensor_desc's
+        with output=True) -> t.  Synchronous; no copy to the host."""
+        if not table_check(table, self.wmb, self.hmb, self.ring):
+            raise CairoError("decode_frame_tensor: table_check refused the table", 3)
+        d = _frame_tensor(t, self.width, self.height, True, desc)
+        tb = np.ascontiguousarray(table).view(np.uint8)
+        coef = np.concatenate([np.ascontiguousarray(p, dtype=np.int16).ravel() for p in planes])
+        assert coef.size == self.wa * self.ha * 3 // 2
+        _ck(self.L.cairo_ctx_decode_frame_tensor(self.h, _ptr(tb), _ptr(coef), index, d.ptr, ctypes.byref(d.c)),
+            "cairo_ctx_decode_frame_tensor")
+        return t
 
     def sync(self) -> None:
         _ck(self.L.cairo_ctx_sync(self.h), "cairo_ctx_sync")
@@ -991,6 +1196,18 @@ class Stream:
             self._keep[t.value] = rgb
         return t.value
 
+    def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, **desc) -> int:
+        """A tensor frame, as Context.submit_tensor (cairo_stream_submit_tensor);
+        t is kept alive until the frame is collected."""
+        d = _frame_tensor(t, self.ctx.width, self.ctx.height, False, desc)
+        if sync:
+            _sync_producer(d.owner)
+        tk = ctypes.c_int()
+        _ck(self.L.cairo_stream_submit_tensor(self.h, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
+                                              ctypes.byref(tk)), "cairo_stream_submit_tensor")
+        self._keep[tk.value] = d
+        return tk.value
+
     def collect(self, ticket: int, out: np.ndarray | None = None, pos: int = 0):
         """Append the frame's payload at bit pos of out -> new pos; with out
         None, return (bytes, nbits) of the payload alone."""
@@ -1104,6 +1321,17 @@ class Encoder:
         _ck(self.L.evx_encoder_set_input_format(self.h, fmt, pitch), "set_input_format")
         self._fmt, self._pitch = fmt, pitch
 
+    def set_input_tensor(self, t, **desc) -> None:
+        """encode() reads, from now on, device tensors laid out like t
+        (tensor_desc's arguments: dtype, strides and the input map are fixed
+        here; each encode() brings a tensor of that layout, such as batch[n] of
+        an NCHW batch, or a device address with width and height).  None goes
+        back to the pixel formats.  Callable between frames."""
+        d = None if t is None else tensor_desc(t, output=False, **desc)
+        _ck(self.L.evx_encoder_set_input_tensor(self.h, None if d is None else ctypes.byref(d.c)),
+            "set_input_tensor")
+        self._tensor = d
+
     def set_input_color(self, range: int, matrix: int) -> None:
         """The colour description (RANGE_*, MATRIX_*) of the I420 / NV12 frames
         encode() reads from now on; callable between frames."""
@@ -1125,6 +1353,20 @@ class Encoder:
         width, 3) RGB888.  After set_input_format, it is a uint8 buffer of
         frame_layout(fmt, width, height, pitch) bytes; width and height may be
         left out where the array's shape is (height, width, 3)."""
+        if getattr(self, "_tensor", None) is not None:
+            # a device tensor laid out as set_input_tensor's, or its address
+            if hasattr(rgb, "data_ptr"):
+                d = tensor_desc(rgb)
+                if tuple(d.c.stride) != tuple(self._tensor.c.stride) or d.c.dtype != self._tensor.c.dtype:
+                    raise ValueError("the tensor's dtype or strides differ from set_input_tensor's")
+                width, height = d.width, d.height
+                _sync_producer(rgb)
+                rgb = d.ptr
+            if width is None or height is None:
+                raise ValueError("width and height are needed with a device address")
+            _ck(self.L.evx_encoder_encode(self.h, int(rgb), width, height, bs.h), "encode")
+            self._shape = (width, height)
+            return
         fmt, pitch = getattr(self, "_fmt", FMT_RGB24), getattr(self, "_pitch", 0)
         if fmt != FMT_RGB24 or pitch:
             if width is None or height is None:
@@ -1183,6 +1425,15 @@ class Decoder:
         _ck(self.L.evx_decoder_set_output_format(self.h, fmt, pitch), "set_output_format")
         self._fmt, self._pitch = fmt, pitch
 
+    def set_output_tensor(self, t, **desc) -> None:
+        """decode(..., out=x) writes, from now on, into device tensors laid out
+        like t (tensor_desc's arguments with output=True), with no copy to the
+        host.  None goes back to the pixel formats.  Callable between frames."""
+        d = None if t is None else tensor_desc(t, output=True, **desc)
+        _ck(self.L.evx_decoder_set_output_tensor(self.h, None if d is None else ctypes.byref(d.c)),
+            "set_output_tensor")
+        self._tensor = d
+
     def set_output_color(self, range: int, matrix: int) -> None:
         """The colour description (RANGE_*, MATRIX_*) decode() writes I420 /
         NV12 frames in from now on; callable between frames."""
@@ -1193,6 +1444,19 @@ class Decoder:
         (h, w, 3) for tight RGB24 / BGR24; for a YUV or pitched output format a
         flat uint8 buffer of frame_layout bytes (split_frame gives its planes).
         out: a buffer to write into (its pitch padding keeps its bytes)."""
+        if getattr(self, "_tensor", None) is not None:
+            # into a device tensor laid out as set_output_tensor's (or its address) -> out
+            if out is None:
+                raise ValueError("decode() into a tensor needs out=")
+            ptr = out
+            if hasattr(out, "data_ptr"):
+                d = tensor_desc(out, output=True)
+                if tuple(d.c.stride) != tuple(self._tensor.c.stride) or d.c.dtype != self._tensor.c.dtype or \
+                        (d.width, d.height) != (width, height):
+                    raise ValueError("the tensor's dtype, strides or size differ from set_output_tensor's")
+                ptr = d.ptr
+            _ck(self.L.evx_decoder_decode(self.h, bs.h, int(ptr)), "decode")
+            return out
         fmt, pitch = getattr(self, "_fmt", FMT_RGB24), getattr(self, "_pitch", 0)
         nb, tight = frame_layout(fmt, width, height, pitch)
         if out is None:

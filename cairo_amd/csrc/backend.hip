@@ -36,6 +36,7 @@
 #include "metrics.h"
 #include "precode.h"
 #include "scale.h"
+#include "tensor.h"
 
 using namespace cairo;
 
@@ -226,6 +227,11 @@ struct cairo_ctx {
   // whose k_scale_batch fills the slot before the convert reads it.
   bool pend_scaled[kMaxBatch] = {};
   ScaleFrame pend_scale[kMaxBatch] = {};
+  // A tensor frame (cairo_ctx_submit_tensor) likewise: a device
+  // frame whose f.rgb is its staging slot, tight RGB24, which the launch's
+  // k_tensor_pack_batch fills from the tensor before the convert reads it.
+  bool pend_tensor[kMaxBatch] = {};
+  TensorFrame pend_tens[kMaxBatch] = {};
   int npend = 0;
   int last_slot = -1;  // slot of the last launched frame
   uint32_t last_epoch = 0;  // and its epoch (the tag of its inter records)
@@ -687,6 +693,27 @@ int flush(cairo_ctx* c) {
       c->pend_scaled[i] = false;
     }
     if (sa.nframes) CK(launch_scale_batch(sa, st));
+  }
+  // Tensor frames: one k_tensor_pack_batch fills their staging slots, under
+  // the same rule (more than kTensorFrames of them take a second kernel).
+  {
+    TensorArgs ta;
+    ta.w = (int)c->w, ta.h = (int)c->h, ta.nframes = 0, ta.reserved = 0;
+    for (int i = 0; i < e.nframes; i++) {
+      if (!c->pend_tensor[i]) continue;
+      Stage& s = c->st[c->pend[i].slot];
+      if (s.rgb_pending) {
+        CK(hipStreamWaitEvent(st, s.rgb_read, 0));
+        s.rgb_pending = false;
+      }
+      ta.f[ta.nframes++] = c->pend_tens[i];
+      c->pend_tensor[i] = false;
+      if (ta.nframes == kTensorFrames) {
+        CK(launch_tensor_pack_batch(ta, st));
+        ta.nframes = 0;
+      }
+    }
+    if (ta.nframes) CK(launch_tensor_pack_batch(ta, st));
   }
   // A launch of tight RGB24 frames keeps k_convert_batch, whose behaviour
   // beside the running launch is measured; any other
@@ -1169,14 +1196,20 @@ int cairo_ctx_busy_intervals(cairo_ctx* c, double* out, int cap, int* n) {
 // the source's size and pitch is the source's: the frame is recorded as a
 // device frame whose f.rgb is its staging slot, tight, which the launch's
 // k_scale_batch fills from the source (flush).
+// With a tensor description (cairo_ctx_submit_tensor) rgb is element (0, 0, 0)
+// of a device tensor: recorded the same way, tight RGB24 in the slot, which the
+// launch's k_tensor_pack_batch fills.
 static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch, bool check_range,
                         uint32_t index, uint32_t type, uint32_t quality, int* ticket,
-                        const cairo_source* scaled = nullptr) {
+                        const cairo_source* scaled = nullptr, const cairo_tensor* tens = nullptr) {
   if (!c || !rgb || !ticket || quality < 1 || quality > 31 || type > 1) return kInvalidArg;
   uint64_t frame_bytes = 0;
   uint32_t tight = 0;
   ScaleFrame plan{};
-  if (scaled) {
+  if (tens) {  // frame_bytes: the span
+    if (tensor_check(tens, rgb, c->w, c->h, &frame_bytes) != kSuccess) return kInvalidArg;
+    tight = 3 * c->w;
+  } else if (scaled) {
     // (the scaler's grid has a row per plane row: at most 65535)
     if (2ull * c->h > 65535 || scale_plan(fmt, pitch, scaled, c->w, c->h, rgb, nullptr, &plan) != kSuccess ||
         cairo_frame_layout(fmt, scaled->width, scaled->height, pitch, &frame_bytes, nullptr) != kSuccess ||
@@ -1198,7 +1231,10 @@ static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int
     hipPointerAttribute_t pa;
     if (hipPointerGetAttributes(&pa, rgb) != hipSuccess || pa.type != hipMemoryTypeDevice || pa.device != c->device) {
       (void)hipGetLastError();
-      if (scaled)
+      if (tens)
+        fprintf(stderr, "[cairo_amd] submit_tensor: %p is not device memory of device %d (a host tensor is not taken: "
+                "the 3*W*H staging slot cannot stage a float frame)\n", (const void*)rgb, c->device);
+      else if (scaled)
         fprintf(stderr, "[cairo_amd] submit_scaled: the source %p is not device memory of device %d (a host source is "
                 "not scaled: upload it once and submit the device frame)\n", (const void*)rgb, c->device);
       else
@@ -1212,23 +1248,35 @@ static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int
       if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)rgb) != hipSuccess ||
           (uint64_t)((const uint8_t*)rgb - (const uint8_t*)base) + frame_bytes > (uint64_t)size) {
         (void)hipGetLastError();
-        fprintf(stderr, "[cairo_amd] submit: a format %d frame with pitch %u (%llu bytes) at %p does not fit its allocation\n",
-                fmt, scaled ? plan.pitch : (pitch ? pitch : tight), (unsigned long long)frame_bytes, (const void*)rgb);
+        if (tens)
+          fprintf(stderr, "[cairo_amd] submit_tensor: the tensor's span (%llu bytes) at %p does not fit its allocation\n",
+                  (unsigned long long)frame_bytes, (const void*)rgb);
+        else
+          fprintf(stderr, "[cairo_amd] submit: a format %d frame with pitch %u (%llu bytes) at %p does not fit its allocation\n",
+                  fmt, scaled ? plan.pitch : (pitch ? pitch : tight), (unsigned long long)frame_bytes, (const void*)rgb);
         return kInvalidArg;
       }
     }
   }
   FrameDesc& f = c->pend[c->npend];
   c->pend_fmt[c->npend] = (uint8_t)fmt;
-  c->pend_pitch[c->npend] = rgb_on_device && pitch && !scaled ? pitch : tight;  // a host frame is staged tight
+  c->pend_pitch[c->npend] = rgb_on_device && pitch && !scaled && !tens ? pitch : tight;  // a host frame is staged tight
   c->pend_hpitch[c->npend] = pitch;
   c->pend_col[c->npend] = fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_NV12 ? (uint8_t)c->in_col : 0;
   c->pend_scaled[c->npend] = scaled != nullptr;
+  c->pend_tensor[c->npend] = tens != nullptr;
   if (scaled) {  // scaled into the slot at launch, tight
     f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
     f.host_rgb = nullptr;
     plan.dst = const_cast<uint8_t*>(f.rgb);
     c->pend_scale[c->npend] = plan;
+  } else if (tens) {  // packed into the slot at launch, tight RGB24
+    f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
+    f.host_rgb = nullptr;
+    TensorFrame& tf = c->pend_tens[c->npend];
+    tf.tensor = const_cast<uint8_t*>(rgb);
+    tf.rgb = const_cast<uint8_t*>(f.rgb);
+    tf.d = *tens;
   } else if (rgb_on_device) {
     f.rgb = rgb;
     f.host_rgb = nullptr;
@@ -1311,6 +1359,13 @@ int cairo_ctx_submit_scaled(cairo_ctx* c, const uint8_t* frame, int fmt, uint32_
                             uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (!src) return kInvalidArg;
   return submit_frame(c, frame, 1, fmt, pitch, true, index, type, quality, ticket, src);
+}
+
+int cairo_ctx_submit_tensor(cairo_ctx* c, const void* base, const cairo_tensor* desc, uint32_t index, uint32_t type,
+                            uint32_t quality, int* ticket) {
+  if (!desc) return kInvalidArg;
+  return submit_frame(c, (const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, index, type, quality, ticket, nullptr,
+                      desc);
 }
 
 static const char* timeout_kind_name(int k) {
@@ -1458,19 +1513,57 @@ static int download_frame(const cairo_ctx* c, uint8_t* dst, const uint8_t* stage
   return kSuccess;
 }
 
+// Whether [p, p + bytes) is device memory of the context's GPU inside one
+// allocation (a tensor the unpack kernel is about to write).
+static bool device_span(const cairo_ctx* c, const void* p, uint64_t bytes, const char* who) {
+  hipPointerAttribute_t pa;
+  if (hipPointerGetAttributes(&pa, p) != hipSuccess || pa.type != hipMemoryTypeDevice || pa.device != c->device) {
+    (void)hipGetLastError();
+    fprintf(stderr, "[cairo_amd] %s: %p is not device memory of device %d (a host tensor is not taken)\n", who, p,
+            c->device);
+    return false;
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess ||
+      (uint64_t)((const uint8_t*)p - (const uint8_t*)base) + bytes > (uint64_t)size) {
+    (void)hipGetLastError();
+    fprintf(stderr, "[cairo_amd] %s: the tensor's span (%llu bytes) at %p does not fit its allocation\n", who,
+            (unsigned long long)bytes, p);
+    return false;
+  }
+  return true;
+}
+
+// The tight RGB888 frame staged at `staged` through the output map into the
+// tensor at tbase (checked by the caller).  Asynchronous on st.
+static int unpack_to_tensor(const cairo_ctx* c, uint8_t* staged, void* tbase, const cairo_tensor* tens,
+                            hipStream_t st) {
+  TensorArgs ta;
+  ta.w = (int)c->w, ta.h = (int)c->h, ta.nframes = 1, ta.reserved = 0;
+  ta.f[0].tensor = (uint8_t*)tbase, ta.f[0].rgb = staged, ta.f[0].d = *tens;
+  return fail(launch_tensor_unpack(ta, st), "launch_tensor_unpack");
+}
+
 // cairo_ctx_decode_frame (fmt < 0: RGB888 through k_yuv_to_rgb, as ever) and
 // cairo_ctx_decode_frame_fmt (k_planes_to_fmt, tight in the staging slot; the
 // D2H copy is 2D per plane when the caller's frame is pitched).
+// With a tensor description (cairo_ctx_decode_frame_tensor) rgb is element
+// (0, 0, 0) of a device tensor: RGB888 into the slot as for fmt < 0, then
+// k_tensor_unpack into the tensor instead of the download.
 static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, int fmt,
-                        uint32_t pitch, uint8_t* rgb) {
+                        uint32_t pitch, uint8_t* rgb, const cairo_tensor* tens = nullptr) {
   if (!c || !table || !coef || !rgb) return kInvalidArg;
   uint64_t frame_bytes = (uint64_t)c->w * c->h * 3;
   uint32_t tight = 3 * c->w;
+  uint64_t span = 0;
+  if (tens && tensor_check(tens, rgb, c->w, c->h, &span) != kSuccess) return kInvalidArg;
   if (fmt >= 0 && cairo_frame_layout(fmt, c->w, c->h, pitch, nullptr, &tight) != kSuccess) return kInvalidArg;
   if (fmt >= 0) (void)cairo_frame_layout(fmt, c->w, c->h, 0, &frame_bytes, nullptr);  // as staged: tight
   std::lock_guard<std::mutex> lk(c->mu);
   if (c->gsize > 1) return kInvalidResource;
   CK(hipSetDevice(c->device));
+  if (tens && !device_span(c, rgb, span, "decode_frame_tensor")) return kInvalidArg;
   int r = flush(c);  // encode frames still pending go first, in their own launch
   if (r) return r;
   const int t = c->next_ticket, slot = t % c->stages;
@@ -1491,6 +1584,7 @@ static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef,
   f.host_table = reinterpret_cast<const BlockDesc*>(table);
   f.host_coef = coef;
   c->pend_scaled[0] = false;
+  c->pend_tensor[0] = false;
   c->npend = 1;
   s.busy = true;
   s.launched = false;
@@ -1515,7 +1609,10 @@ static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef,
     if (r == kSuccess)
       r = fail(hipMemcpyAsync(s.err, c->sticky, TimeoutInfo::kWords * sizeof(int32_t), hipMemcpyDeviceToHost, st),
                "hipMemcpyAsync");
-    if (r == kSuccess) r = download_frame(c, rgb, drgb, fmt, pitch, tight, frame_bytes, st);
+    if (r == kSuccess && tens)
+      r = unpack_to_tensor(c, drgb, rgb, tens, st);
+    else if (r == kSuccess)
+      r = download_frame(c, rgb, drgb, fmt, pitch, tight, frame_bytes, st);
     if (r == kSuccess) r = fail(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (r == kSuccess && s.err[TimeoutInfo::kKind]) {
       report_timeout_host(c, s.err, index, st);  // (mu held: the launch stream, idle now)
@@ -1535,6 +1632,12 @@ int cairo_ctx_decode_frame_fmt(cairo_ctx* c, const uint8_t* table, const int16_t
                                uint32_t pitch, uint8_t* out) {
   if (fmt < 0) return kInvalidArg;
   return decode_frame(c, table, coef, index, fmt, pitch, out);
+}
+
+int cairo_ctx_decode_frame_tensor(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, void* base,
+                                  const cairo_tensor* desc) {
+  if (!desc) return kInvalidArg;
+  return decode_frame(c, table, coef, index, -1, 0, (uint8_t*)base, desc);
 }
 
 static bool color_known(int range, int matrix) {
@@ -1712,6 +1815,26 @@ int cairo_ctx_fetch_recon(cairo_ctx* c, int ticket, int fmt, uint32_t pitch, uin
   CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, fmt, tight, staged,
                           c->out_col, c->fs));
   const int r = download_frame(c, out, staged, fmt, pitch, tight, frame_bytes, c->fs);
+  if (r) return r;
+  CK(hipStreamSynchronize(c->fs));
+  return kSuccess;
+}
+
+int cairo_ctx_fetch_recon_tensor(cairo_ctx* c, int ticket, void* base, const cairo_tensor* desc) {
+  if (!c || !base || !desc) return kInvalidArg;
+  uint64_t span = 0;
+  if (tensor_check(desc, base, c->w, c->h, &span) != kSuccess) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!kept_stage(c, ticket)) return kInvalidArg;
+  CK(hipSetDevice(c->device));
+  if (!device_span(c, base, span, "fetch_recon_tensor")) return kInvalidArg;
+  if (!c->fs) CK(hipStreamCreateWithFlags(&c->fs, hipStreamNonBlocking));
+  // staged in the slot's frame buffer as tight RGB24, as cairo_ctx_fetch_recon does
+  const int slot = ticket % c->stages;
+  uint8_t* staged = c->rgb + (size_t)slot * c->w * c->h * 3;
+  CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, CAIRO_FMT_RGB24, 3 * c->w,
+                          staged, c->out_col, c->fs));
+  const int r = unpack_to_tensor(c, staged, base, desc, c->fs);
   if (r) return r;
   CK(hipStreamSynchronize(c->fs));
   return kSuccess;

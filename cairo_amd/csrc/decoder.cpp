@@ -58,7 +58,8 @@ class gpu_decoder : public evx1_decoder {
     const uint8_t *tbl = reinterpret_cast<const uint8_t *>(table_);
     // the engine trusts the table: a stream it cannot honour is an error
     if (!cairo_table_check(tbl, wmb_, hmb_, ring_)) return EVX_ERROR_EXECUTION_FAILURE;
-    if (fmt_ == CAIRO_FMT_RGB24 && !pitch_
+    if (tensor_ ? cairo_ctx_decode_frame_tensor(ctx_, tbl, coef_, f.index, output, &tens_)
+        : fmt_ == CAIRO_FMT_RGB24 && !pitch_
             ? cairo_ctx_decode_frame(ctx_, tbl, coef_, f.index, static_cast<uint8_t *>(output))
             : cairo_ctx_decode_frame_fmt(ctx_, tbl, coef_, f.index, fmt_, pitch_, static_cast<uint8_t *>(output)))
       return EVX_ERROR_EXECUTION_FAILURE;
@@ -79,6 +80,15 @@ class gpu_decoder : public evx1_decoder {
     if (cairo_frame_layout(fmt, w, h, initialized_ ? pitch : 0, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
     fmt_ = fmt;
     pitch_ = pitch;
+    return EVX_SUCCESS;
+  }
+  // decode()'s output as a device tensor written through desc (between frames
+  // too; nullptr: back to the pixel formats).  Its strides are checked against
+  // the frame size at each decode().
+  evx_status set_output_tensor(const cairo_tensor *desc) {
+    if (desc && cairo_tensor_check(desc, nullptr, 1, 1, nullptr)) return EVX_ERROR_INVALIDARG;
+    tensor_ = desc != nullptr;
+    if (desc) tens_ = *desc;
     return EVX_SUCCESS;
   }
   // The colour description decode() writes I420 / NV12 frames in (between
@@ -136,6 +146,8 @@ class gpu_decoder : public evx1_decoder {
   int device_ = 0;
   int fmt_ = CAIRO_FMT_RGB24;  // output layout (set_output_format)
   uint32 pitch_ = 0;
+  bool tensor_ = false;  // set_output_tensor: output is a device tensor written through tens_
+  cairo_tensor tens_{};
   int range_ = CAIRO_RANGE_FULL, matrix_ = CAIRO_MATRIX_BT601;  // set_output_color
   cairo_ctx *ctx_ = nullptr;
   cairo::BlockDesc *table_ = nullptr;
@@ -174,6 +186,9 @@ int evx_decoder_set_device(void *dec, int device) {
 }
 int evx_decoder_set_output_format(void *dec, int fmt, uint32_t pitch) {
   return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_output_format(fmt, pitch);
+}
+int evx_decoder_set_output_tensor(void *dec, const cairo_tensor *desc) {
+  return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_output_tensor(desc);
 }
 int evx_decoder_set_output_color(void *dec, int range, int matrix) {
   return static_cast<evx::gpu_decoder *>((evx::evx1_decoder *)dec)->set_output_color(range, matrix);

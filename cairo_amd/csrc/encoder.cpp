@@ -80,13 +80,18 @@ class gpu_encoder : public evx1_encoder {
       if (evx_failed(output->write_bytes(&h, sizeof(h)))) return EVX_ERROR_EXECUTION_FAILURE;
     }
     if (width != width_ || height != height_) return EVX_ERROR_INVALID_RESOURCE;
-    if (cairo_frame_layout(fmt_, width, height, pitch_, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
+    if (tensor_) {
+      if (cairo_tensor_check(&tens_, image, width, height, nullptr)) return EVX_ERROR_INVALIDARG;
+    } else if (cairo_frame_layout(fmt_, width, height, pitch_, nullptr, nullptr)) {
+      return EVX_ERROR_INVALIDARG;
+    }
     frame_t f = frame_;
     if (evx_failed(output->write_bytes(&f, sizeof(f)))) return EVX_ERROR_EXECUTION_FAILURE;
 
     const auto t0 = std::chrono::steady_clock::now();
     int ticket = -1;
-    int r = fmt_ == CAIRO_FMT_RGB24 && !pitch_
+    int r = tensor_ ? cairo_ctx_submit_tensor(ctx_, image, &tens_, frame_.index, frame_.type, frame_.quality, &ticket)
+            : fmt_ == CAIRO_FMT_RGB24 && !pitch_
                 ? cairo_ctx_submit(ctx_, (const uint8_t *)image, 0, frame_.index, frame_.type, frame_.quality,
                                    &ticket)
                 : cairo_ctx_submit_fmt(ctx_, (const uint8_t *)image, 0, fmt_, pitch_, frame_.index, frame_.type,
@@ -205,6 +210,15 @@ class gpu_encoder : public evx1_encoder {
     pitch_ = pitch;
     return EVX_SUCCESS;
   }
+  // encode()'s image as a device tensor read through desc (between frames too;
+  // nullptr: back to the pixel formats).  Its strides are checked against the
+  // frame size at each encode().
+  evx_status set_input_tensor(const cairo_tensor *desc) {
+    if (desc && cairo_tensor_check(desc, nullptr, 1, 1, nullptr)) return EVX_ERROR_INVALIDARG;
+    tensor_ = desc != nullptr;
+    if (desc) tens_ = *desc;
+    return EVX_SUCCESS;
+  }
   // The colour description of the I420 / NV12 images encode() reads (between
   // frames too; RGB images ignore it).
   evx_status set_input_color(int range, int matrix) {
@@ -264,6 +278,8 @@ class gpu_encoder : public evx1_encoder {
   int device_ = 0;
   int fmt_ = CAIRO_FMT_RGB24;  // input layout (set_input_format)
   uint32 pitch_ = 0;
+  bool tensor_ = false;  // set_input_tensor: image is a device tensor read through tens_
+  cairo_tensor tens_{};
   int range_ = CAIRO_RANGE_FULL, matrix_ = CAIRO_MATRIX_BT601;  // set_input_color
   cairo_ctx *ctx_ = nullptr;
   uint8 *last_table_ = nullptr;
@@ -312,6 +328,9 @@ int evx_encoder_set_device(void *enc, int device) {
 }
 int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch) {
   return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_format(fmt, pitch);
+}
+int evx_encoder_set_input_tensor(void *enc, const cairo_tensor *desc) {
+  return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_tensor(desc);
 }
 int evx_encoder_set_input_color(void *enc, int range, int matrix) {
   return static_cast<evx::gpu_encoder *>((evx::evx1_encoder *)enc)->set_input_color(range, matrix);

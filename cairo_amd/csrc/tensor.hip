@@ -1,0 +1,322 @@
+// cairo_amd/csrc/tensor.hip -- tensor frames: a strided uint8 / float16 /
+// bfloat16 / float32 tensor in device memory to the tight RGB24 frame of a
+// staging slot (k_tensor_pack_batch, the tensor submit's pre-pass) and back
+// (k_tensor_unpack: a decoded frame or a kept reconstruction written straight
+// into the caller's tensor).  include/cairo_amd.h, cairo_tensor; DESIGN.md
+// §4.15.  The sample map itself is tensor_pixel.h, shared with the host.
+//
+// Like the scaled submit's pre-pass, the pack kernel runs before the launch's
+// convert kernel and writes the frame's staging slot, which k_convert_batch
+// then reads as it reads an uploaded host frame: the convert kernels and the
+// engine are untouched.
+//
+// Work split: a thread owns 4 consecutive pixels of one row (the last strip of
+// a row may hold fewer), 128 threads per workgroup, grid = (ceil(W / 512), H,
+// frames).  On the tensor side each channel's 4 elements are one 4 / 8 / 16
+// byte access where the column stride is 1, the strip is whole and its address
+// is aligned to the access; otherwise they are element accesses.  On the RGB24
+// side the strip's 12 bytes are three dword accesses where the strip is whole
+// and its address is a multiple of 4, else byte accesses.  Nothing outside the
+// W x H elements of the three channels is read or written on the tensor side,
+// nothing outside the tight frame on the RGB24 side.  No LDS, no scratch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <utility>
+
+#include "../../include/cairo_amd.h"
+#include "tensor.h"
+#include "tensor_pixel.h"
+
+namespace cairo {
+
+namespace {
+
+constexpr int kTensorThreads = 128;  // a workgroup spans 512 pixels of one row
+constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
+constexpr uint64_t kMaxSpanElems = 1ull << 40;
+
+template <uint32_t DT>
+struct ElemSize {
+  static constexpr int v = DT == kDtU8 ? 1 : (DT == kDtF32 ? 4 : 2);
+};
+
+// The element bits of columns 0..n-1 of a strip (zero beyond n).  p: column 0;
+// step: bytes from one column to the next; vec: the 4 elements are contiguous,
+// all inside the row, and p is aligned to the 4-element access.
+template <uint32_t DT>
+__device__ __forceinline__ void load_elems(const uint8_t* p, int64_t step, bool vec, int n, uint32_t bits[4]) {
+  constexpr int ES = ElemSize<DT>::v;
+  if (vec) {
+    if (ES == 1) {
+      const uint32_t v = *(const uint32_t*)p;
+#pragma unroll
+      for (int k = 0; k < 4; k++) bits[k] = (v >> (8 * k)) & 255u;
+    } else if (ES == 2) {
+      const uint2 v = *(const uint2*)p;
+      bits[0] = v.x & 0xFFFFu, bits[1] = v.x >> 16, bits[2] = v.y & 0xFFFFu, bits[3] = v.y >> 16;
+    } else {
+      const uint4 v = *(const uint4*)p;
+      bits[0] = v.x, bits[1] = v.y, bits[2] = v.z, bits[3] = v.w;
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    bits[k] = 0;
+    if (k < n) {
+      const uint8_t* e = p + k * step;
+      bits[k] = ES == 1 ? (uint32_t)*e : (ES == 2 ? (uint32_t) * (const uint16_t*)e : *(const uint32_t*)e);
+    }
+  }
+}
+
+template <uint32_t DT>
+__device__ __forceinline__ void store_elems(uint8_t* p, int64_t step, bool vec, int n, const uint32_t bits[4]) {
+  constexpr int ES = ElemSize<DT>::v;
+  if (vec) {
+    if (ES == 1) {
+      *(uint32_t*)p = bits[0] | (bits[1] << 8) | (bits[2] << 16) | (bits[3] << 24);
+    } else if (ES == 2) {
+      *(uint2*)p = make_uint2(bits[0] | (bits[1] << 16), bits[2] | (bits[3] << 16));
+    } else {
+      *(uint4*)p = make_uint4(bits[0], bits[1], bits[2], bits[3]);
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    if (k < n) {
+      uint8_t* e = p + k * step;
+      if (ES == 1)
+        *e = (uint8_t)bits[k];
+      else if (ES == 2)
+        *(uint16_t*)e = (uint16_t)bits[k];
+      else
+        *(uint32_t*)e = bits[k];
+    }
+  }
+}
+
+// A strip of the frame: row y, pixels px0 .. px0 + n - 1.
+struct Strip {
+  int y, px0, n;
+  uint8_t* rgb;  // the strip's first RGB24 byte
+  bool rgb_vec;  // whole and dword-aligned: three dword accesses
+};
+
+__device__ __forceinline__ bool make_strip(const TensorArgs& a, const TensorFrame& f, Strip* s) {
+  s->y = (int)blockIdx.y;
+  s->px0 = 4 * (int)(blockIdx.x * kTensorThreads + threadIdx.x);
+  if (s->y >= a.h || s->px0 >= a.w) return false;
+  s->n = min(4, a.w - s->px0);
+  s->rgb = f.rgb + ((size_t)s->y * (size_t)a.w + (size_t)s->px0) * 3;
+  s->rgb_vec = s->n == 4 && ((uintptr_t)s->rgb & 3) == 0;
+  return true;
+}
+
+// Channel c's column 0 of the strip, the column step in bytes, and whether the
+// 4 elements are one aligned access.
+template <uint32_t DT>
+__device__ __forceinline__ uint8_t* channel_at(const TensorFrame& f, const Strip& s, int c, int64_t* step, bool* vec) {
+  constexpr int ES = ElemSize<DT>::v;
+  const int64_t e = (int64_t)c * f.d.stride[0] + (int64_t)s.y * f.d.stride[1] + (int64_t)s.px0 * f.d.stride[2];
+  uint8_t* p = f.tensor + e * ES;
+  *step = f.d.stride[2] * ES;
+  *vec = f.d.stride[2] == 1 && s.n == 4 && ((uintptr_t)p & (uintptr_t)(4 * ES - 1)) == 0;
+  return p;
+}
+
+template <uint32_t DT>
+__device__ __forceinline__ void pack_strip(const TensorFrame& f, const Strip& s) {
+  uint32_t smp[3][4];  // [channel][pixel], each pinned by tensor_sat8
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    int64_t step;
+    bool vec;
+    const uint8_t* p = channel_at<DT>(f, s, c, &step, &vec);
+    uint32_t bits[4];
+    load_elems<DT>(p, step, vec, s.n, bits);
+#pragma unroll
+    for (int k = 0; k < 4; k++) smp[c][k] = tensor_pack_sample(DT, bits[k], f.d.mul[c], f.d.add[c]);
+  }
+  if (s.rgb_vec) {
+    uint32_t d[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const int b = 3 * k + c;
+        d[b >> 2] |= smp[c][k] << (8 * (b & 3));
+      }
+    uint32_t* o = (uint32_t*)s.rgb;
+    o[0] = d[0], o[1] = d[1], o[2] = d[2];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < s.n) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) s.rgb[3 * k + c] = (uint8_t)smp[c][k];
+      }
+  }
+}
+
+template <uint32_t DT>
+__device__ __forceinline__ void unpack_strip(const TensorFrame& f, const Strip& s) {
+  uint32_t smp[3][4];
+  if (s.rgb_vec) {
+    const uint32_t* i = (const uint32_t*)s.rgb;
+    const uint32_t d[3] = {i[0], i[1], i[2]};
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const int b = 3 * k + c;
+        smp[c][k] = (d[b >> 2] >> (8 * (b & 3))) & 255u;
+      }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) smp[c][k] = k < s.n ? (uint32_t)s.rgb[3 * k + c] : 0u;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    int64_t step;
+    bool vec;
+    uint8_t* p = channel_at<DT>(f, s, c, &step, &vec);
+    uint32_t bits[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) bits[k] = tensor_unpack_sample(DT, smp[c][k], f.d.mul[c], f.d.add[c]);
+    store_elems<DT>(p, step, vec, s.n, bits);
+  }
+}
+
+// grid: x strips of a row, y row, z tensor frame of the launch.  The dtype is
+// uniform over the workgroup.
+__global__ __launch_bounds__(kTensorThreads) void k_tensor_pack_batch(TensorArgs a) {
+  const TensorFrame& f = a.f[blockIdx.z];
+  Strip s;
+  if (!make_strip(a, f, &s)) return;
+  switch (f.d.dtype) {
+    case kDtU8: pack_strip<kDtU8>(f, s); break;
+    case kDtF16: pack_strip<kDtF16>(f, s); break;
+    case kDtBf16: pack_strip<kDtBf16>(f, s); break;
+    default: pack_strip<kDtF32>(f, s); break;
+  }
+}
+
+__global__ __launch_bounds__(kTensorThreads) void k_tensor_unpack(TensorArgs a) {
+  const TensorFrame& f = a.f[blockIdx.z];
+  Strip s;
+  if (!make_strip(a, f, &s)) return;
+  switch (f.d.dtype) {
+    case kDtU8: unpack_strip<kDtU8>(f, s); break;
+    case kDtF16: unpack_strip<kDtF16>(f, s); break;
+    case kDtBf16: unpack_strip<kDtBf16>(f, s); break;
+    default: unpack_strip<kDtF32>(f, s); break;
+  }
+}
+
+int fail(hipError_t e, const char* what) {
+  if (e == hipSuccess) return kSuccess;
+  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
+  return kHardwareFail;
+}
+
+bool launch_ok(const TensorArgs& a) {
+  return a.nframes >= 1 && a.nframes <= kTensorFrames && a.w >= 1 && a.h >= 1 && a.h <= 65535;
+}
+dim3 tensor_grid(const TensorArgs& a) {
+  return dim3((unsigned)((a.w + 4 * kTensorThreads - 1) / (4 * kTensorThreads)), (unsigned)a.h, (unsigned)a.nframes);
+}
+
+}  // namespace
+
+int tensor_check(const cairo_tensor* d, const void* base, uint32_t w, uint32_t h, uint64_t* span_bytes) {
+  if (!d || !w || !h || h > 65535) return kInvalidArg;
+  if (d->dtype > kDtF32 || d->reserved0 || d->reserved[0] || d->reserved[1]) return kInvalidArg;
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(d->mul[c]) || !std::isfinite(d->add[c])) return kInvalidArg;
+  const uint32_t es = tensor_elem_size(d->dtype);
+  if ((uintptr_t)base % es) return kInvalidArg;
+  // (stride, extent) sorted by stride, ties by extent: each dimension must
+  // step over everything the smaller ones cover
+  std::pair<int64_t, uint64_t> p[3] = {{d->stride[0], 3}, {d->stride[1], h}, {d->stride[2], w}};
+  std::sort(p, p + 3);
+  if (p[0].first < 1) return kInvalidArg;
+  unsigned __int128 span = 1;
+  for (int i = 0; i < 3; i++) {
+    if (i && (unsigned __int128)p[i].first < (unsigned __int128)p[i - 1].first * p[i - 1].second) return kInvalidArg;
+    span += (unsigned __int128)(p[i].second - 1) * (uint64_t)p[i].first;
+    if (span > kMaxSpanElems) return kInvalidArg;
+  }
+  if (span_bytes) *span_bytes = (uint64_t)span * es;
+  return kSuccess;
+}
+
+hipError_t launch_tensor_pack_batch(const TensorArgs& a, hipStream_t s) {
+  if (!launch_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tensor_pack_batch, tensor_grid(a), dim3(kTensorThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tensor_unpack(const TensorArgs& a, hipStream_t s) {
+  if (!launch_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tensor_unpack, tensor_grid(a), dim3(kTensorThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace cairo
+
+using namespace cairo;
+
+extern "C" {
+
+int cairo_tensor_size(void) { return (int)sizeof(cairo_tensor); }
+
+int cairo_tensor_check(const cairo_tensor* desc, const void* base, uint32_t width, uint32_t height,
+                       uint64_t* span_bytes) {
+  return tensor_check(desc, base, width, height, span_bytes);
+}
+
+int cairo_tensor_host(int dir, const cairo_tensor* desc, uint32_t w, uint32_t h, void* tensor, uint8_t* rgb24) {
+  if ((dir != 0 && dir != 1) || !tensor || !rgb24 || tensor_check(desc, tensor, w, h, nullptr) != kSuccess)
+    return kInvalidArg;
+  tensor_host_loops(dir, desc->dtype, desc->stride, desc->mul, desc->add, w, h, (uint8_t*)tensor, rgb24);
+  return kSuccess;
+}
+
+int cairo_kat_tensor(int dir, const cairo_tensor* desc, uint32_t w, uint32_t h, void* tensor, uint64_t tensor_bytes,
+                     uint8_t* rgb24, int device) {
+  uint64_t span = 0;
+  if ((dir != 0 && dir != 1) || !tensor || !rgb24 || tensor_check(desc, tensor, w, h, &span) != kSuccess ||
+      span > tensor_bytes)
+    return kInvalidArg;
+  int r = fail(hipSetDevice(device), "hipSetDevice");
+  if (r) return r;
+  const size_t rbytes = (size_t)w * h * 3 + CAIRO_KAT_TENSOR_GUARD;
+  const size_t mis = (uintptr_t)tensor & 15;  // the device copy keeps the tensor's address modulo 16
+  uint8_t *dt = nullptr, *dr = nullptr;
+  TensorArgs* a = new TensorArgs();
+  a->w = (int)w, a->h = (int)h, a->nframes = 1;
+  if ((r = fail(hipMalloc(&dt, tensor_bytes + 16), "malloc")) || (r = fail(hipMalloc(&dr, rbytes), "malloc"))) goto done;
+  a->f[0].tensor = dt + mis, a->f[0].rgb = dr, a->f[0].d = *desc;
+  if ((r = fail(hipMemcpy(dt + mis, tensor, tensor_bytes, hipMemcpyHostToDevice), "h2d")) ||
+      (r = fail(hipMemcpy(dr, rgb24, rbytes, hipMemcpyHostToDevice), "h2d")) ||
+      (r = fail(dir ? launch_tensor_unpack(*a, nullptr) : launch_tensor_pack_batch(*a, nullptr), "k_tensor")) ||
+      (r = fail(hipDeviceSynchronize(), "sync")) ||
+      (r = fail(hipMemcpy(tensor, dt + mis, tensor_bytes, hipMemcpyDeviceToHost), "d2h")) ||
+      (r = fail(hipMemcpy(rgb24, dr, rbytes, hipMemcpyDeviceToHost), "d2h")))
+    goto done;
+done:
+  delete a;
+  (void)hipFree(dt);
+  (void)hipFree(dr);
+  return r;
+}
+
+}  // extern "C"

@@ -57,7 +57,12 @@ extern "C" {
  *   4  (unchanged) colour descriptions add entry points only:
  *      cairo_color_coefs, cairo_ctx_set_input_color, cairo_ctx_set_output_color,
  *      cairo_kat_convert_color, evx_encoder_set_input_color,
- *      evx_decoder_set_output_color. */
+ *      evx_decoder_set_output_color.
+ *   4  (unchanged) tensor frames add entry points only: cairo_tensor_size,
+ *      cairo_tensor_check, cairo_tensor_host, cairo_kat_tensor,
+ *      cairo_ctx_submit_tensor, cairo_stream_submit_tensor,
+ *      cairo_ctx_decode_frame_tensor, cairo_ctx_fetch_recon_tensor,
+ *      evx_encoder_set_input_tensor, evx_decoder_set_output_tensor. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -271,6 +276,85 @@ CAIRO_API int cairo_ctx_submit_scaled(cairo_ctx *ctx, const uint8_t *frame, int 
 CAIRO_API int cairo_kat_scale(int fmt, uint32_t pitch, const cairo_source *src, const uint8_t *frame,
                               uint32_t dst_w, uint32_t dst_h, uint8_t *out, int device);
 
+/* ---- tensor frames -----------------------------------------
+ * A frame that already lives in device memory as a tensor -- a model's output,
+ * a loader's input -- is taken and written in place: planar or channels-last,
+ * uint8 / float16 / bfloat16 / float32, values in any affine range, with any
+ * positive strides (a frame of an NCHW batch, a channels_last view, a crop, the
+ * RGB channels of an RGBA tensor). */
+#define CAIRO_DT_U8   0
+#define CAIRO_DT_F16  1   /* IEEE binary16 */
+#define CAIRO_DT_BF16 2
+#define CAIRO_DT_F32  3
+typedef struct cairo_tensor {
+  uint32_t dtype;        /* CAIRO_DT_*                                            */
+  uint32_t reserved0;    /* 0                                                     */
+  int64_t  stride[3];    /* in elements: channel (R,G,B = 0,1,2), row, column; >0 */
+  float    mul[3], add[3];  /* per channel, finite                                */
+  uint32_t reserved[2];  /* 0                                                     */
+} cairo_tensor;
+/* Element (c, y, x) is at base + (c*stride[0] + y*stride[1] + x*stride[2]) *
+ * elem_size; the width W and height H are the context's.
+ *
+ * The map, in IEEE binary32, one stated rounding per step, nothing else:
+ *   in  (dir 0), tensor element to 8-bit sample s:
+ *     x = (float)element                      (exact for all four dtypes,
+ *                                              float16 subnormals included)
+ *     t = fmaf(x, mul[c], add[c])
+ *     s = isnan(t) ? 0 : (int)min(max(rintf(t), 0.f), 255.f)
+ *                                             (nearest, ties to even; +-inf clamp)
+ *   out (dir 1), sample s to tensor element:
+ *     t = fmaf((float)s, mul[c], add[c])
+ *     F32: t.  F16 / BF16: t rounded to nearest even, overflow to infinity,
+ *     subnormals kept.  U8: the clamp and round of dir 0.
+ * For values in [0, 1]: in mul = 255, add = 0; out mul = 1/255, add = 0.
+ *
+ * Everything else is what a tight RGB24 frame gets: a tensor submit produces
+ * exactly the bits of submitting pack(tensor) as RGB24, and a frame decoded
+ * into a tensor is unpack of the RGB24 frame cairo_ctx_decode_frame writes.
+ *
+ * Validity (EVX_ERROR_INVALID_ARGS otherwise): a known dtype, reserved words
+ * 0, finite mul and add, base aligned to the element size, 1 <= H <= 65535,
+ * and no two elements at one address: the (stride, extent) pairs with extents
+ * (3, H, W), sorted ascending by stride (ties by extent) into (s1,e1), (s2,e2),
+ * (s3,e3), satisfy s1 >= 1, s2 >= s1*e1 and s3 >= s2*e2.  The span
+ * 1 + sum (e_i - 1) * s_i is at most 2^40 elements.  Negative strides, BGR
+ * order, host tensors and integer dtypes other than uint8 are not taken. */
+/* sizeof(cairo_tensor), for bindings. */
+CAIRO_API int cairo_tensor_size(void);
+/* Validity of desc for a width x height frame at address base (only its
+ * alignment is looked at); *span_bytes (may be NULL) receives the span in
+ * bytes.  Host only, no device needed. */
+CAIRO_API int cairo_tensor_check(const cairo_tensor *desc, const void *base, uint32_t width, uint32_t height,
+                                 uint64_t *span_bytes);
+/* The map as plain host loops, on host buffers: dir 0 reads tensor and writes
+ * the tight RGB24 frame rgb24 (3*w*h bytes), dir 1 the reverse, writing only
+ * the elements the descriptor covers.  The same per-sample code as the
+ * kernels.  No device needed. */
+CAIRO_API int cairo_tensor_host(int dir, const cairo_tensor *desc, uint32_t w, uint32_t h, void *tensor,
+                                uint8_t *rgb24);
+/* Known-answer check of the tensor kernels on host buffers, without a context
+ * or the engine.  tensor is tensor_bytes long from element (0,0,0) (at least
+ * the span); rgb24 holds the tight frame followed by CAIRO_KAT_TENSOR_GUARD
+ * bytes.  Both are uploaded first and both are read back, so the bytes a
+ * kernel must not touch can be checked.  The device copy of tensor keeps
+ * tensor's address modulo 16, so a misaligned base can be checked. */
+#define CAIRO_KAT_TENSOR_GUARD 64
+CAIRO_API int cairo_kat_tensor(int dir, const cairo_tensor *desc, uint32_t w, uint32_t h, void *tensor,
+                               uint64_t tensor_bytes, uint8_t *rgb24, int device);
+/* cairo_ctx_submit of the RGB24 frame the input map gives.  base is device
+ * memory of this context's GPU; the whole span lies inside one allocation (a
+ * framework's sub-allocated block passes).  It is read when the frame's batch
+ * launches, by one pre-pass kernel per launch that fills the frames' staging
+ * slots, and must stay valid and unchanged until the frame's wait; the caller
+ * orders its producer before the submit, as for any device frame.  A host
+ * pointer is refused: the 3*W*H staging slot cannot stage a float frame.  A
+ * launch may mix tensor frames of any dtype, strides and map with frames of
+ * the pixel formats.  A refused submit takes no ticket.  Allowed for group
+ * members. */
+CAIRO_API int cairo_ctx_submit_tensor(cairo_ctx *ctx, const void *base, const cairo_tensor *desc, uint32_t index,
+                                      uint32_t type, uint32_t quality, int *ticket);
+
 /* Wait until the frame's block table and coefficients are host-visible. */
 CAIRO_API int cairo_ctx_wait(cairo_ctx *ctx, int ticket, cairo_frame_result *out);
 /* The decoder's hot path (decode_slice + deblock + convert_image,
@@ -287,6 +371,14 @@ CAIRO_API int cairo_ctx_decode_frame(cairo_ctx *ctx, const uint8_t *block_table,
  * bytes). */
 CAIRO_API int cairo_ctx_decode_frame_fmt(cairo_ctx *ctx, const uint8_t *block_table, const int16_t *coef,
                                          uint32_t index, int fmt, uint32_t pitch, uint8_t *out);
+/* The same, written into a tensor in device memory of this context's GPU (the
+ * output map of cairo_tensor; base and desc as for cairo_ctx_submit_tensor):
+ * unpack of the RGB888 frame cairo_ctx_decode_frame writes.  No copy to the
+ * host is made.  Bytes of the destination that no element covers (stride
+ * gaps, an alpha channel, everything beyond the span) are never written.
+ * Synchronous, and refused for group members, like cairo_ctx_decode_frame. */
+CAIRO_API int cairo_ctx_decode_frame_tensor(cairo_ctx *ctx, const uint8_t *block_table, const int16_t *coef,
+                                            uint32_t index, void *base, const cairo_tensor *desc);
 /* Hand the ticket's staging buffers back (required before ticket+stages). */
 CAIRO_API int cairo_ctx_release(cairo_ctx *ctx, int ticket);
 /* Launch any pending frames and block until all GPU work is finished. */
@@ -515,6 +607,10 @@ CAIRO_API int cairo_ctx_fetch_recon_planes(cairo_ctx *ctx, int ticket, int16_t *
  * host memory out (cairo_frame_layout bytes; the pitch padding keeps its
  * bytes): what cairo_ctx_decode_frame_fmt writes for this frame. */
 CAIRO_API int cairo_ctx_fetch_recon(cairo_ctx *ctx, int ticket, int fmt, uint32_t pitch, uint8_t *out);
+/* The same frame as RGB888 through the output map into a tensor in device
+ * memory (cairo_ctx_decode_frame_tensor's rules): what
+ * cairo_ctx_decode_frame_tensor writes for this frame. */
+CAIRO_API int cairo_ctx_fetch_recon_tensor(cairo_ctx *ctx, int ticket, void *base, const cairo_tensor *desc);
 /* Known-answer check of the metrics kernels on host buffers, without a
  * context or the engine: planes a and b of w x h (luma; chroma (w/2) x (h/2))
  * with pitch_elems elements per luma row and pitch_elems / 2 per chroma row
@@ -626,6 +722,9 @@ CAIRO_API int cairo_stream_submit_fmt(cairo_stream *s, const uint8_t *frame, int
 CAIRO_API int cairo_stream_submit_scaled(cairo_stream *s, const uint8_t *frame, int fmt, uint32_t pitch,
                                          const cairo_source *src, uint32_t index, uint32_t type,
                                          uint32_t quality, int *ticket);
+/* cairo_stream_submit for a tensor frame (cairo_ctx_submit_tensor). */
+CAIRO_API int cairo_stream_submit_tensor(cairo_stream *s, const void *base, const cairo_tensor *desc, uint32_t index,
+                                         uint32_t type, uint32_t quality, int *ticket);
 /* Wait for the frame's payload and append it at bit *bit_pos of out
  * (out_bytes capacity, LSB-first; out == NULL only advances *bit_pos).  If it
  * does not fit, returns EVX_ERROR_CAPACITY_LIMIT (7) and keeps the payload:
@@ -669,6 +768,12 @@ CAIRO_API int evx_encoder_set_input_format(void *enc, int fmt, uint32_t pitch);
 /* The colour description of the I420 / NV12 images encode() reads from now on
  * (cairo_ctx_set_input_color); callable between frames. */
 CAIRO_API int evx_encoder_set_input_color(void *enc, int range, int matrix);
+/* encode()'s image is, from now on, the address of element (0,0,0) of a tensor
+ * in device memory of the encoder's GPU, read through desc
+ * (cairo_ctx_submit_tensor; the frame size is still encode()'s width and
+ * height).  desc == NULL goes back to the pixel formats.  Callable between
+ * frames.  peek() is unchanged. */
+CAIRO_API int evx_encoder_set_input_tensor(void *enc, const cairo_tensor *desc);
 /* CAIRO_METRIC_* for the frames encode() codes from now on (callable between
  * frames), and the metrics of the last encoded frame (EVX_ERROR_INVALID_ARGS
  * when it has none). */
@@ -690,6 +795,11 @@ CAIRO_API int evx_decoder_set_output_format(void *dec, int fmt, uint32_t pitch);
 /* The colour description decode() writes I420 / NV12 frames in from now on
  * (cairo_ctx_set_output_color); callable between frames. */
 CAIRO_API int evx_decoder_set_output_color(void *dec, int range, int matrix);
+/* decode()'s output is, from now on, the address of element (0,0,0) of a
+ * tensor in device memory of the decoder's GPU, written through desc
+ * (cairo_ctx_decode_frame_tensor).  desc == NULL goes back to the pixel
+ * formats.  Callable between frames. */
+CAIRO_API int evx_decoder_set_output_tensor(void *dec, const cairo_tensor *desc);
 
 /* bit_stream (reference bitstream.h:43-92) */
 CAIRO_API void *evx_bitstream_create(uint32_t size_in_bits);
