@@ -617,6 +617,47 @@ def _view(addr: int, dtype, count: int) -> np.ndarray:
     return np.frombuffer(buf, dtype=dtype, count=count)
 
 
+def _submit(prefix: str, handle, width: int, height: int, keep: dict, rgb, index: int, inter: bool, quality: int,
+            on_device: bool, fmt: int, pitch: int, src_size, crop) -> int:
+    """Context.submit and Stream.submit: prefix is "cairo_ctx" or
+    "cairo_stream", handle its object, width x height the context's frame size,
+    keep the caller's ticket -> host frame map.  Tight RGB24 takes the plain
+    call, which does not range-check a device frame."""
+    L = lib()
+    t = ctypes.c_int()
+    if src_size is not None or crop is not None:
+        if src_size is None:
+            raise ValueError("crop needs src_size")
+        s = _source(src_size, crop)
+        ptr = _scaled_source_ptr(rgb, on_device, fmt, src_size, pitch)
+        _ck(getattr(L, prefix + "_submit_scaled")(handle, ptr, fmt, pitch, ctypes.byref(s), index, int(inter), quality,
+                                                  ctypes.byref(t)), prefix + "_submit_scaled")
+        return t.value
+    ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, width, height, pitch)
+    if fmt == FMT_RGB24 and not pitch:
+        _ck(getattr(L, prefix + "_submit")(handle, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
+            prefix + "_submit")
+    else:
+        _ck(getattr(L, prefix + "_submit_fmt")(handle, ptr, int(on_device), fmt, pitch, index, int(inter), quality,
+                                               ctypes.byref(t)), prefix + "_submit_fmt")
+    if not on_device:  # the H2D copy is asynchronous: keep the host frame alive
+        keep[t.value] = rgb
+    return t.value
+
+
+def _submit_tensor(prefix: str, handle, width: int, height: int, keep: dict, t, index: int, inter: bool, quality: int,
+                   sync: bool, desc: dict) -> int:
+    """Context.submit_tensor and Stream.submit_tensor, as _submit."""
+    d = _frame_tensor(t, width, height, False, desc)
+    if sync:
+        _sync_producer(d.owner)
+    tk = ctypes.c_int()
+    _ck(getattr(lib(), prefix + "_submit_tensor")(handle, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
+                                                  ctypes.byref(tk)), prefix + "_submit_tensor")
+    keep[tk.value] = d
+    return tk.value
+
+
 class Context:
     """The encode-path backend (``cairo_ctx_*``): one encoder's device state."""
 
@@ -653,27 +694,8 @@ class Context:
         pitch), scaled to the context's size on the GPU before it is encoded
         (cairo_ctx_submit_scaled, see scale_check); crop = (x, y, w, h) scales a
         region of it."""
-        t = ctypes.c_int()
-        if src_size is not None or crop is not None:
-            if src_size is None:
-                raise ValueError("crop needs src_size")
-            s = _source(src_size, crop)
-            ptr = _scaled_source_ptr(rgb, on_device, fmt, src_size, pitch)
-            _ck(self.L.cairo_ctx_submit_scaled(self.h, ptr, fmt, pitch, ctypes.byref(s), index, int(inter), quality,
-                                               ctypes.byref(t)), "cairo_ctx_submit_scaled")
-            return t.value
-        ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, self.width, self.height, pitch)
-        if fmt == FMT_RGB24 and not pitch:
-            _ck(
-                self.L.cairo_ctx_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
-                "cairo_ctx_submit",
-            )
-        else:
-            _ck(self.L.cairo_ctx_submit_fmt(self.h, ptr, int(on_device), fmt, pitch, index, int(inter), quality,
-                                            ctypes.byref(t)), "cairo_ctx_submit_fmt")
-        if not on_device:  # the H2D copy is asynchronous: keep the host frame alive
-            self._keep[t.value] = rgb
-        return t.value
+        return _submit("cairo_ctx", self.h, self.width, self.height, self._keep, rgb, index, inter, quality, on_device,
+                       fmt, pitch, src_size, crop)
 
     def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, **desc) -> int:
         """Submit a tensor frame in device memory (cairo_ctx_submit_tensor): t
@@ -683,14 +705,8 @@ class Context:
         change before it.  sync: synchronise the producer's current stream
         first when torch is already imported (the C ABI leaves that ordering to
         the caller)."""
-        d = _frame_tensor(t, self.width, self.height, False, desc)
-        if sync:
-            _sync_producer(d.owner)
-        tk = ctypes.c_int()
-        _ck(self.L.cairo_ctx_submit_tensor(self.h, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
-                                           ctypes.byref(tk)), "cairo_ctx_submit_tensor")
-        self._keep[tk.value] = d
-        return tk.value
+        return _submit_tensor("cairo_ctx", self.h, self.width, self.height, self._keep, t, index, inter, quality, sync,
+                              desc)
 
     def wait(self, ticket: int, copy: bool = True) -> FrameOutputs:
         r = _FrameResult()
@@ -1176,37 +1192,14 @@ class Stream:
     def submit(self, rgb, index: int, inter: bool, quality: int, on_device: bool = False,
                fmt: int = FMT_RGB24, pitch: int = 0, src_size=None, crop=None) -> int:
         """src_size / crop: a scaled submit, as Context.submit."""
-        t = ctypes.c_int()
-        if src_size is not None or crop is not None:
-            if src_size is None:
-                raise ValueError("crop needs src_size")
-            s = _source(src_size, crop)
-            ptr = _scaled_source_ptr(rgb, on_device, fmt, src_size, pitch)
-            _ck(self.L.cairo_stream_submit_scaled(self.h, ptr, fmt, pitch, ctypes.byref(s), index, int(inter), quality,
-                                                  ctypes.byref(t)), "cairo_stream_submit_scaled")
-            return t.value
-        ptr = rgb if on_device else _host_frame_fmt(rgb, fmt, self.ctx.width, self.ctx.height, pitch)
-        if fmt == FMT_RGB24 and not pitch:
-            _ck(self.L.cairo_stream_submit(self.h, ptr, int(on_device), index, int(inter), quality, ctypes.byref(t)),
-                "cairo_stream_submit")
-        else:
-            _ck(self.L.cairo_stream_submit_fmt(self.h, ptr, int(on_device), fmt, pitch, index, int(inter), quality,
-                                               ctypes.byref(t)), "cairo_stream_submit_fmt")
-        if not on_device:
-            self._keep[t.value] = rgb
-        return t.value
+        return _submit("cairo_stream", self.h, self.ctx.width, self.ctx.height, self._keep, rgb, index, inter, quality,
+                       on_device, fmt, pitch, src_size, crop)
 
     def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, **desc) -> int:
         """A tensor frame, as Context.submit_tensor (cairo_stream_submit_tensor);
         t is kept alive until the frame is collected."""
-        d = _frame_tensor(t, self.ctx.width, self.ctx.height, False, desc)
-        if sync:
-            _sync_producer(d.owner)
-        tk = ctypes.c_int()
-        _ck(self.L.cairo_stream_submit_tensor(self.h, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
-                                              ctypes.byref(tk)), "cairo_stream_submit_tensor")
-        self._keep[tk.value] = d
-        return tk.value
+        return _submit_tensor("cairo_stream", self.h, self.ctx.width, self.ctx.height, self._keep, t, index, inter,
+                              quality, sync, desc)
 
     def collect(self, ticket: int, out: np.ndarray | None = None, pos: int = 0):
         """Append the frame's payload at bit pos of out -> new pos; with out

@@ -96,6 +96,14 @@ struct Stage {
   uint32_t index = 0, type = 0, quality = 0;
 };
 
+// Ticket t takes the stage (submit, decode_frame).
+void take_stage(Stage& s, int t, uint32_t index, uint32_t type, uint32_t quality, int mflags) {
+  s.busy = true, s.launched = false, s.waited = false;
+  s.mflags = mflags;
+  s.ticket = t;
+  s.index = index, s.type = type, s.quality = quality;
+}
+
 struct TimedBatch {
   hipEvent_t ev[kTimed + 1] = {};
   int frames = 0;
@@ -210,28 +218,34 @@ struct cairo_ctx {
   int next_ticket = 0;
   uint32_t epoch = 0;
   int batch_max = 16;
-  FrameDesc pend[kMaxBatch];
-  // Layout of each pending frame as the convert kernel reads it (CAIRO_FMT_*,
-  // row pitch in bytes): a device frame's own, a staged host frame's tight
-  // one.  pend_hpitch: the pitch of a host source still to upload (flush).
-  uint8_t pend_fmt[kMaxBatch] = {};
-  uint32_t pend_pitch[kMaxBatch] = {}, pend_hpitch[kMaxBatch] = {};
+  // A pending frame: its FrameDesc and how the launch reads its pixels, all of
+  // it written at submit (decode_frame: its one frame); flush() only reads it.
+  struct Pending {
+    // kStaged: a host frame, staged tight in its slot (uploaded at submit; in a
+    // group at launch).  kDevice: a device frame read in place.  kScaled
+    // (cairo_ctx_submit_scaled), kTensor (cairo_ctx_submit_tensor, DESIGN
+    // §4.15): f.rgb is the staging slot, tight, which the launch's k_scale_batch
+    // / k_tensor_pack_batch fills from `scale` / `tens` before the convert.
+    enum Kind : uint8_t { kStaged, kDevice, kScaled, kTensor };
+    FrameDesc f;
+    Kind kind;
+    // Layout as the convert kernel reads it (CAIRO_FMT_*, row pitch in bytes):
+    // a device frame's own, a staged frame's tight one.  hpitch: the pitch of a
+    // host source still to upload (flush).  col: the input colour description
+    // in force at submit (kernels.h color_index; 0 for an RGB frame).
+    uint8_t fmt, col;
+    uint32_t pitch, hpitch;
+    union {
+      ScaleFrame scale;
+      TensorFrame tens;
+    };
+  };
+  Pending pend[kMaxBatch];
   // Colour descriptions (cairo_ctx_set_input_color / _output_color, DESIGN
   // §4.13) as kernels.h color_index values: in_col is recorded per frame at
-  // submit (pend_col; 0 for an RGB frame), out_col is read when a frame is
-  // written as I420 / NV12.  Neither is touched by cairo_ctx_reset.
-  uint8_t pend_col[kMaxBatch] = {};
+  // submit (Pending::col), out_col is read when a frame is written as I420 /
+  // NV12.  Neither is touched by cairo_ctx_reset.
   int in_col = 0, out_col = 0;
-  // A scaled frame (cairo_ctx_submit_scaled) is a device frame whose f.rgb is
-  // its staging slot, tight; its source and geometry wait here for the launch,
-  // whose k_scale_batch fills the slot before the convert reads it.
-  bool pend_scaled[kMaxBatch] = {};
-  ScaleFrame pend_scale[kMaxBatch] = {};
-  // A tensor frame (cairo_ctx_submit_tensor) likewise: a device
-  // frame whose f.rgb is its staging slot, tight RGB24, which the launch's
-  // k_tensor_pack_batch fills from the tensor before the convert reads it.
-  bool pend_tensor[kMaxBatch] = {};
-  TensorFrame pend_tens[kMaxBatch] = {};
   int npend = 0;
   int last_slot = -1;  // slot of the last launched frame
   uint32_t last_epoch = 0;  // and its epoch (the tag of its inter records)
@@ -268,6 +282,8 @@ struct cairo_ctx {
 };
 
 namespace {
+
+using Pending = cairo_ctx::Pending;
 
 int fail(hipError_t e, const char* what) {
   if (e == hipSuccess) return kSuccess;
@@ -545,50 +561,67 @@ int collect_times(cairo_ctx* c, TimedBatch& t) {
   return kSuccess;
 }
 
-// Upload a host frame of format fmt into a staging slot, packed tight: one
-// copy when the source is tight (pitch 0 or the tight pitch), else a 2D copy
-// per plane.  Every tight format fits the slot's 3 * w * h bytes.
-int upload_frame(const cairo_ctx* c, uint8_t* dst, const uint8_t* src, int fmt, uint32_t pitch, hipStream_t st) {
-  uint64_t bytes = 0;
-  uint32_t tight = 0;
-  if (cairo_frame_layout(fmt, c->w, c->h, 0, &bytes, &tight) != kSuccess) return kInvalidArg;
-  if (!pitch || pitch == tight) {
-    CK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, st));
+// Copy a frame of format fmt (fmt < 0: RGB888) between a staging slot, where it
+// lies tight (every tight format fits the slot's 3 * w * h bytes), and a host
+// frame of the given pitch (0: tight): one copy when that is tight too, else a
+// 2D copy per plane, so a host frame's pitch padding keeps its bytes.
+// Asynchronous on st.
+int copy_frame(const cairo_ctx* c, uint8_t* staged, uint8_t* host, bool upload, int fmt, uint32_t pitch,
+               hipStream_t st) {
+  uint64_t bytes = (uint64_t)c->w * c->h * 3;
+  uint32_t tight = 3 * c->w;
+  if (fmt >= 0 && cairo_frame_layout(fmt, c->w, c->h, 0, &bytes, &tight) != kSuccess) return kInvalidArg;
+  const hipMemcpyKind kind = upload ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  if (fmt < 0 || !pitch || pitch == tight) {
+    CK(hipMemcpyAsync(upload ? staged : host, upload ? host : staged, (size_t)bytes, kind, st));
     return kSuccess;
   }
+  // one plane: `rows` rows of `row` bytes, at soff (pitch sp) in the slot and hoff (pitch hp) in the host frame
+  auto plane = [&](size_t soff, size_t sp, size_t hoff, size_t hp, size_t row, size_t rows) {
+    return upload ? hipMemcpy2DAsync(staged + soff, sp, host + hoff, hp, row, rows, kind, st)
+                  : hipMemcpy2DAsync(host + hoff, hp, staged + soff, sp, row, rows, kind, st);
+  };
   const size_t w = c->w, h = c->h;
-  CK(hipMemcpy2DAsync(dst, tight, src, pitch, tight, h, hipMemcpyHostToDevice, st));  // RGB rows, or the Y plane
-  const uint8_t* sc = src + (size_t)pitch * h;
-  uint8_t* dc = dst + w * h;
+  CK(plane(0, tight, 0, pitch, tight, h));  // RGB rows, or the Y plane
   if (fmt == CAIRO_FMT_I420) {
     const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
-    CK(hipMemcpy2DAsync(dc, cw, sc, cp, cw, ch, hipMemcpyHostToDevice, st));
-    CK(hipMemcpy2DAsync(dc + cw * ch, cw, sc + cp * ch, cp, cw, ch, hipMemcpyHostToDevice, st));
+    CK(plane(w * h, cw, (size_t)pitch * h, cp, cw, ch));
+    CK(plane(w * h + cw * ch, cw, (size_t)pitch * h + cp * ch, cp, cw, ch));
   } else if (fmt == CAIRO_FMT_NV12) {
-    CK(hipMemcpy2DAsync(dc, w, sc, pitch, w, h / 2, hipMemcpyHostToDevice, st));
+    CK(plane(w * h, w, (size_t)pitch * h, pitch, w, h / 2));
   }
   return kSuccess;
 }
 
-// Launch the pending batch.
-int flush(cairo_ctx* c) {
-  if (c->npend == 0) return kSuccess;
-  CK(hipSetDevice(c->device));
-  EngineArgs e = engine_args(c);
+// A staging slot's frame buffer: 3 * w * h bytes, which every tight format fits.
+uint8_t* slot_rgb(const cairo_ctx* c, int slot) { return c->rgb + (size_t)slot * c->w * c->h * 3; }
+
+// One launch of the pending batch, handed from step to step of flush(): the
+// plan, the inputs, the engine, the outputs.
+struct Launch {
+  EngineArgs e;
+  hipStream_t st = nullptr, ost = nullptr;  // the launch's stream; the stream its outputs complete on
+  int fslot = 0, area = 0, rows = 0;
+  FrameArgs *fh = nullptr, *fd = nullptr;  // its frame views: pinned host slot, device copy
+  TimedBatch* tb = nullptr;                // profiling events (nullptr: off)
+};
+
+// Plan: the launch's stream, sync area, frame views, pool split and task
+// queues.
+int plan_launch(cairo_ctx* c, Launch& l) {
+  EngineArgs& e = l.e;
+  e = engine_args(c);
   e.nframes = c->npend;
   // frame descriptors -> device (a ring of pinned slots: the copy of an earlier
   // launch may still be pending when this one is written)
-  const int fslot = c->fdesc_next;
+  const int fslot = l.fslot = c->fdesc_next;
   c->fdesc_next = (c->fdesc_next + 1) % kLaunchSlots;
   if (c->fdesc_used[fslot]) CK(hipEventSynchronize(c->fdesc_done[fslot]));
-  FrameArgs* fh = c->fdesc_host + (size_t)fslot * kMaxBatch;
-  FrameArgs* fd = c->fdesc + (size_t)fslot * kMaxBatch;
-  bool any_inter = false;
-  for (int i = 0; i < c->npend; i++) any_inter |= c->pend[i].inter && c->ring > 1;
+  FrameArgs* fh = l.fh = c->fdesc_host + (size_t)fslot * kMaxBatch;
+  FrameArgs* fd = l.fd = c->fdesc + (size_t)fslot * kMaxBatch;
   e.fa = fd;
-  e.decode = c->pend[0].decode;  // a launch never mixes (decode_frame flushes first)
-  const int rows = e.nframes * e.hmb;
-  (void)any_inter;
+  e.decode = c->pend[0].f.decode;  // a launch never mixes (decode_frame flushes first)
+  const int rows = l.rows = e.nframes * e.hmb;
   // Launch b alternates streams and sync areas; it follows launch b-1, which
   // may still be running: its frame 0 waits on the deblock progress of b-1's
   // last frame (tagged words in that frame's staging slot).  Residency: a
@@ -601,15 +634,15 @@ int flush(cairo_ctx* c) {
   // to b-1's own workers; a batch is complete when its finished-task count
   // says so (k_batch_wait), not when its launch ends.
   const long long b = c->batches++;
-  hipStream_t st = (b & 1) ? c->ks2 : c->ks;
-  const int area = (int)(b % kSyncAreas);
+  l.st = l.ost = (b & 1) ? c->ks2 : c->ks;
+  const int area = l.area = (int)(b % kSyncAreas);
   e.sync = c->sync + (size_t)area * c->sync_words;
   e.pfa = c->prev_fa;
   for (int k = 0; k < 2; k++) e.porder[k] = c->prev_order[k], e.pseg[k] = c->prev_seg[k];
   e.psync = c->prev_sync;
   e.ptotal = c->prev_decode == e.decode ? c->prev_total : 0;  // a worker runs one kind of task
   e.slope = c->order_slope;
-  for (int i = 0; i < c->npend; i++) fh[i] = make_frame_view(e, c->pend[i], i);
+  for (int i = 0; i < c->npend; i++) fh[i] = make_frame_view(e, c->pend[i].f, i);
   {  // half of the resident slots per launch, split between the pools
     const int total = 2 * (c->wg_rows > 0 ? std::min(c->wg_rows, (c->stamps ? 2 : 1) * c->max_rows) : c->max_rows);
     // default split: even, and 25/48 helpers (200 of 384) on large frames
@@ -631,22 +664,29 @@ int flush(cairo_ctx* c) {
   }
   // this sync area was last used by launch b-3 (only a launch reads its own
   // area); launch b-2 precedes this one on the same stream
-  if (b >= 3) CK(hipStreamWaitEvent(st, c->batch_end[(b - 3) % kSyncAreas], 0));
-  TimedBatch* tb = nullptr;
+  if (b >= 3) CK(hipStreamWaitEvent(l.st, c->batch_end[(b - 3) % kSyncAreas], 0));
+  return kSuccess;
+}
+
+// Inputs: the uploads issued at submit, host sources still to upload, the
+// decoder's table and coefficients.
+int enqueue_uploads(cairo_ctx* c, Launch& l) {
+  const hipStream_t st = l.st;
   if (c->profiling) {
-    tb = &c->tb[c->tb_next];
+    l.tb = &c->tb[c->tb_next];
     c->tb_next = (c->tb_next + 1) % kLaunchSlots;
-    int r = collect_times(c, *tb);  // its events are about to be reused
+    int r = collect_times(c, *l.tb);  // its events are about to be reused
     if (r) return r;
   }
   if (c->up_pending) {  // the frames' uploads, issued at submit on the upload stream
     CK(hipStreamWaitEvent(st, c->up_last, 0));
     c->up_pending = false;
   }
-  for (int i = 0; i < e.nframes; i++) {  // host RGB sources; the decoder's table and coefficients
-    const FrameDesc& f = c->pend[i];
+  for (int i = 0; i < l.e.nframes; i++) {  // host RGB sources; the decoder's table and coefficients
+    const FrameDesc& f = c->pend[i].f;
     if (f.host_rgb) {
-      const int r = upload_frame(c, const_cast<uint8_t*>(f.rgb), f.host_rgb, c->pend_fmt[i], c->pend_hpitch[i], st);
+      const int r = copy_frame(c, slot_rgb(c, f.slot), const_cast<uint8_t*>(f.host_rgb), true, c->pend[i].fmt,
+                               c->pend[i].hpitch, st);
       if (r) return r;
     }
     if (f.decode) {
@@ -655,116 +695,128 @@ int flush(cairo_ctx* c) {
       CK(hipMemcpyAsync(coef_base(c, f.slot), f.host_coef, c->plane_elems * 2, hipMemcpyHostToDevice, st));
     }
   }
-  // the frame views and the zeroed sync area are written by the convert
-  // kernel below (ConvertArgs), not by runtime copy / fill kernels
-  ConvertArgs ca{};
-  ca.w = e.w, ca.h = e.h, ca.wa = e.wa, ca.nframes = e.nframes;
-  for (int i = 0; i < e.nframes; i++) {
-    ca.rgb[i] = fh[i].decode ? nullptr : fh[i].rgb;
-    ca.in[i] = fh[i].in;
-  }
-  static_assert(sizeof(FrameArgs) % sizeof(uint4) == 0, "frame views copied in 16-byte chunks");
-  ca.fa_host = (const uint4*)(c->fdesc_host_dev + (size_t)fslot * kMaxBatch);
-  ca.fa_dev = (uint4*)fd;
-  ca.fa_chunks = (int)(sizeof(FrameArgs) * e.nframes / sizeof(uint4));
-  ca.sync = e.sync;
-  ca.sync_words = (int)c->sync_words;
   if (c->stamps) {  // engine entry (min) / exit (max) words
     static const uint64_t init[2] = {~0ull, 0};
     CK(hipMemcpyAsync(c->stamps + kMaxBatch * stamp_frame_words((int)c->wmb, (int)c->hmb), init, sizeof(init),
                       hipMemcpyHostToDevice, st));
   }
-  if (tb) CK(hipEventRecord(tb->ev[0], st));
-  // Scaled frames: one k_scale_batch fills their staging slots before the
-  // convert reads them.  A launch without one enqueues nothing here.  A slot's
-  // previous frame may have been converted on the other launch stream (a
-  // ticket may be released unwaited): wait for that convert (rgb_read).
-  {
-    ScaleArgs sa;
-    sa.dw = (int)c->w, sa.dh = (int)c->h, sa.nframes = 0, sa.reserved = 0;
-    for (int i = 0; i < e.nframes; i++) {
-      if (!c->pend_scaled[i]) continue;
-      Stage& s = c->st[c->pend[i].slot];
-      if (s.rgb_pending) {
-        CK(hipStreamWaitEvent(st, s.rgb_read, 0));
-        s.rgb_pending = false;
-      }
-      sa.f[sa.nframes++] = c->pend_scale[i];
-      c->pend_scaled[i] = false;
+  if (l.tb) CK(hipEventRecord(l.tb->ev[0], st));
+  return kSuccess;
+}
+
+// Inputs: the pre-pass of one kind of frame (scaled: k_scale_batch, tensor:
+// k_tensor_pack_batch) fills those frames' staging slots before the convert
+// reads them: one kernel, and another whenever its argument block is full.
+// A launch without such a frame enqueues nothing here.  A slot's previous
+// frame may have been converted on the other launch stream (a ticket may be
+// released unwaited): wait for that convert (rgb_read).
+template <class Args, class Frame>
+int enqueue_prepass(cairo_ctx* c, const Launch& l, Pending::Kind kind, Frame Pending::*frame,
+                    hipError_t (*launch)(const Args&, hipStream_t)) {
+  Args a;  // only the header is written here: both blocks are {frame width, height, nframes, reserved, f[]}
+  auto& [aw, ah, an, ares, af] = a;
+  aw = (int)c->w, ah = (int)c->h, an = 0, ares = 0;
+  constexpr int cap = (int)(sizeof(af) / sizeof(af[0]));
+  for (int i = 0; i < l.e.nframes; i++) {
+    if (c->pend[i].kind != kind) continue;
+    Stage& s = c->st[c->pend[i].f.slot];
+    if (s.rgb_pending) {
+      CK(hipStreamWaitEvent(l.st, s.rgb_read, 0));
+      s.rgb_pending = false;
     }
-    if (sa.nframes) CK(launch_scale_batch(sa, st));
-  }
-  // Tensor frames: one k_tensor_pack_batch fills their staging slots, under
-  // the same rule (more than kTensorFrames of them take a second kernel).
-  {
-    TensorArgs ta;
-    ta.w = (int)c->w, ta.h = (int)c->h, ta.nframes = 0, ta.reserved = 0;
-    for (int i = 0; i < e.nframes; i++) {
-      if (!c->pend_tensor[i]) continue;
-      Stage& s = c->st[c->pend[i].slot];
-      if (s.rgb_pending) {
-        CK(hipStreamWaitEvent(st, s.rgb_read, 0));
-        s.rgb_pending = false;
-      }
-      ta.f[ta.nframes++] = c->pend_tens[i];
-      c->pend_tensor[i] = false;
-      if (ta.nframes == kTensorFrames) {
-        CK(launch_tensor_pack_batch(ta, st));
-        ta.nframes = 0;
-      }
+    af[an++] = c->pend[i].*frame;
+    if (an == cap) {
+      CK(launch(a, l.st));
+      an = 0;
     }
-    if (ta.nframes) CK(launch_tensor_pack_batch(ta, st));
   }
+  if (an) CK(launch(a, l.st));
+  return kSuccess;
+}
+
+// Inputs: the convert, which also writes the frame views and zeroes the sync
+// area, then the records that say so (rgb_read, fdesc_done, batch_ready).
+int enqueue_convert(cairo_ctx* c, Launch& l) {
+  const EngineArgs& e = l.e;
+  const hipStream_t st = l.st;
+  // the frame views and the zeroed sync area are written by the convert
+  // kernel below (ConvertArgs), not by runtime copy / fill kernels
+  ConvertArgs ca{};
+  ca.w = e.w, ca.h = e.h, ca.wa = e.wa, ca.nframes = e.nframes;
+  for (int i = 0; i < e.nframes; i++) {
+    ca.rgb[i] = l.fh[i].decode ? nullptr : l.fh[i].rgb;
+    ca.in[i] = l.fh[i].in;
+  }
+  static_assert(sizeof(FrameArgs) % sizeof(uint4) == 0, "frame views copied in 16-byte chunks");
+  ca.fa_host = (const uint4*)(c->fdesc_host_dev + (size_t)l.fslot * kMaxBatch);
+  ca.fa_dev = (uint4*)l.fd;
+  ca.fa_chunks = (int)(sizeof(FrameArgs) * e.nframes / sizeof(uint4));
+  ca.sync = e.sync;
+  ca.sync_words = (int)c->sync_words;
   // A launch of tight RGB24 frames keeps k_convert_batch, whose behaviour
   // beside the running launch is measured; any other
   // layout in the launch takes all of its frames through k_convert_fmt_batch
   // (a colour description belongs to a YUV frame, which is never tight RGB24).
   bool tight_rgb = true;
   for (int i = 0; i < e.nframes; i++)
-    tight_rgb &= !ca.rgb[i] || (c->pend_fmt[i] == CAIRO_FMT_RGB24 && c->pend_pitch[i] == 3 * c->w);
+    tight_rgb &= !ca.rgb[i] || (c->pend[i].fmt == CAIRO_FMT_RGB24 && c->pend[i].pitch == 3 * c->w);
   if (tight_rgb) {
     CK(launch_convert_batch(ca, st));
   } else {
     ConvertFmtArgs cf{};
     cf.c = ca;
     for (int i = 0; i < e.nframes; i++)
-      cf.fmt[i] = c->pend_fmt[i], cf.pitch[i] = c->pend_pitch[i], cf.col[i] = c->pend_col[i];
+      cf.fmt[i] = c->pend[i].fmt, cf.pitch[i] = c->pend[i].pitch, cf.col[i] = c->pend[i].col;
     CK(launch_convert_fmt_batch(cf, st));
   }
-  CK(hipEventRecord(c->fdesc_done[fslot], st));  // fh has been read
-  c->fdesc_used[fslot] = true;
+  CK(hipEventRecord(c->fdesc_done[l.fslot], st));  // fh has been read
+  c->fdesc_used[l.fslot] = true;
   // (a staged frame of any format starts at its slot's address)
   for (int i = 0; i < e.nframes; i++) {  // staged host RGB converted: the buffer may be refilled
-    const FrameDesc& f = c->pend[i];
+    const FrameDesc& f = c->pend[i].f;
     Stage& s = c->st[f.slot];
-    if (!f.decode && f.rgb == c->rgb + (size_t)f.slot * c->w * c->h * 3) {
+    if (!f.decode && f.rgb == slot_rgb(c, f.slot)) {
       CK(hipEventRecord(s.rgb_read, st));
       s.rgb_pending = true;
     }
   }
-  CK(hipEventRecord(c->batch_ready[area], st));
+  CK(hipEventRecord(c->batch_ready[l.area], st));
   // the previous batch's tasks, which this launch's workers may run, need its
   // frames converted and its views and sync area in place
   if (e.ptotal) CK(hipStreamWaitEvent(st, c->batch_ready[c->prev_area], 0));
+  return kSuccess;
+}
+
+// Engine: k_engine, and the kernel that waits for the batch.
+int enqueue_engine(cairo_ctx* c, Launch& l) {
+  const EngineArgs& e = l.e;
+  const hipStream_t st = l.st;
+  TimedBatch* tb = l.tb;
   if (tb) CK(hipEventRecord(tb->ev[1], st));
   if (tb) CK(hipEventRecord(tb->ev[2], st));
   CK(launch_engine(e, st));
   // the launch ends when its workers find no task left; its batch is done
   // when every task has finished (the next launch's workers may run the last)
-  CK(launch_batch_wait(e.sync, 2 * rows, c->sticky, st));
-  c->prev_fa = fd;
+  CK(launch_batch_wait(e.sync, 2 * l.rows, c->sticky, st));
+  c->prev_fa = l.fd;
   for (int k = 0; k < 2; k++) c->prev_order[k] = e.order[k], c->prev_seg[k] = e.seg[k];
   c->prev_sync = e.sync;
-  c->prev_total = rows;
-  c->prev_area = area;
+  c->prev_total = l.rows;
+  c->prev_area = l.area;
   c->prev_decode = e.decode;
   if (tb) {
     CK(hipEventRecord(tb->ev[3], st));
     tb->frames = e.nframes;
     tb->pending = true;
   }
-  const int last = c->pend[e.nframes - 1].slot;
-  const uint32_t last_epoch = c->pend[e.nframes - 1].epoch;
+  return kSuccess;
+}
+
+// Outputs: the debug pre-deblock unpack, the per-frame metrics, the precode and
+// its feed copy (l.ost becomes the stream that copy runs on).
+int enqueue_results(cairo_ctx* c, Launch& l) {
+  const EngineArgs& e = l.e;
+  const hipStream_t st = l.st;
   if (c->predeblock) CK(launch_unpack_granules(e, e.nframes - 1, planes_at(c->predeblock, c), st));
   // Per-frame metrics: one launch for the batch, after k_batch_wait on the
   // launch's stream (every push store of the batch has been drained by then,
@@ -776,9 +828,9 @@ int flush(cairo_ctx* c) {
     ma.w = e.w, ma.h = e.h, ma.pitch = e.wa;
     ma.flags = c->metrics;
     for (int i = 0; i < e.nframes; i++) {
-      if (c->pend[i].decode) continue;
-      const int slot = c->pend[i].slot;
-      ma.a[ma.nframes] = fh[i].in;
+      if (c->pend[i].f.decode) continue;
+      const int slot = c->pend[i].f.slot;
+      ma.a[ma.nframes] = l.fh[i].in;
       ma.b[ma.nframes] = slot_planes(c->keep, c, slot);
       ma.slot[ma.nframes++] = slot;
     }
@@ -786,61 +838,66 @@ int flush(cairo_ctx* c) {
     ma.out = c->met_dev;
     CK(launch_metrics(ma, st));
   }
-  hipStream_t ost = st;  // the stream the launch's outputs complete on
-  if (c->outputs & CAIRO_OUT_FEED) {  // the entropy precode, straight into mapped host memory
-    FeedArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.nframes = e.nframes;
-    fa.fa = fd;
-    for (int i = 0; i < e.nframes; i++) {
-      fa.slot[i] = c->pend[i].slot;
-      fa.host[i] = c->feed_host + (size_t)fa.slot[i] * (kFeedHdrWords + c->feed_words);
-    }
-    fa.scratch = c->feed_scratch;
-    fa.scratch_stride = feed_scratch_words(c->mbs);
-    fa.feed = c->feed_dev;
-    fa.feed_stride = c->feed_words;
-    fa.hdr = c->feed_hdr;
-    // each frame's block table and the timeout words go to its mapped pinned
-    // stage in the same kernel as the feed: no D2H copy per frame, whose
-    // shader blit waits for a workgroup slot of the persistent engine
-    for (int i = 0; i < e.nframes; i++) {
-      const Stage& s = c->st[fa.slot[i]];
-      fa.table_host[i] = c->pend[i].decode ? nullptr : (uint4*)s.table_dev;
-      fa.err_host[i] = c->pend[i].decode ? nullptr : s.err_dev;
-    }
-    fa.table_words = (int)(c->mbs * sizeof(BlockDesc) / sizeof(uint4));
-    CK(launch_precode(fa, (int)c->mbs, st));
-    // The copy into the mapped host stages is PCIe-bound and no engine
-    // launch needs it: on the copy stream, so that the launch two ahead on
-    // this stream starts without it (+0.2 %, profiles/r06/ab_4k_feed_copy_aside.txt).
-    // Not when the copy stream carries host-RGB uploads (submit): those must
-    // not queue behind a feed copy that waits for its launch.
-    if (!c->host_uploads) {
-      CK(hipEventRecord(c->pre_done[area], st));
-      CK(hipStreamWaitEvent(c->cs, c->pre_done[area], 0));
-      CK(launch_feed_copy(fa, c->cs));
-      ost = c->cs;
-    } else {
-      CK(launch_feed_copy(fa, st));
-    }
+  if (!(c->outputs & CAIRO_OUT_FEED)) return kSuccess;
+  FeedArgs fa;  // the entropy precode, straight into mapped host memory
+  memset(&fa, 0, sizeof(fa));
+  fa.nframes = e.nframes;
+  fa.fa = l.fd;
+  for (int i = 0; i < e.nframes; i++) {
+    fa.slot[i] = c->pend[i].f.slot;
+    fa.host[i] = c->feed_host + (size_t)fa.slot[i] * (kFeedHdrWords + c->feed_words);
   }
-  CK(hipEventRecord(c->batch_end[area], ost));
+  fa.scratch = c->feed_scratch;
+  fa.scratch_stride = feed_scratch_words(c->mbs);
+  fa.feed = c->feed_dev;
+  fa.feed_stride = c->feed_words;
+  fa.hdr = c->feed_hdr;
+  // each frame's block table and the timeout words go to its mapped pinned
+  // stage in the same kernel as the feed: no D2H copy per frame, whose
+  // shader blit waits for a workgroup slot of the persistent engine
+  for (int i = 0; i < e.nframes; i++) {
+    const Stage& s = c->st[fa.slot[i]];
+    fa.table_host[i] = c->pend[i].f.decode ? nullptr : (uint4*)s.table_dev;
+    fa.err_host[i] = c->pend[i].f.decode ? nullptr : s.err_dev;
+  }
+  fa.table_words = (int)(c->mbs * sizeof(BlockDesc) / sizeof(uint4));
+  CK(launch_precode(fa, (int)c->mbs, st));
+  // The copy into the mapped host stages is PCIe-bound and no engine
+  // launch needs it: on the copy stream, so that the launch two ahead on
+  // this stream starts without it (+0.2 %, profiles/r06/ab_4k_feed_copy_aside.txt).
+  // Not when the copy stream carries host-RGB uploads (submit): those must
+  // not queue behind a feed copy that waits for its launch.
+  if (!c->host_uploads) {
+    CK(hipEventRecord(c->pre_done[l.area], st));
+    CK(hipStreamWaitEvent(c->cs, c->pre_done[l.area], 0));
+    CK(launch_feed_copy(fa, c->cs));
+    l.ost = c->cs;
+  } else {
+    CK(launch_feed_copy(fa, st));
+  }
+  return kSuccess;
+}
+
+// Outputs: the end of the batch, then each frame's copies to the host and its
+// d2h_done.
+int enqueue_copies(cairo_ctx* c, const Launch& l) {
+  const hipStream_t ost = l.ost;
+  CK(hipEventRecord(c->batch_end[l.area], ost));
   // the copy stream carries the outputs' copies to the host: the feed copies
   // (k_feed_copy, above) or the host-RGB uploads (submit), and with the
   // coefficient planes their D2H copies (the uploads then go on a stream of
   // their own)
   if ((c->outputs & CAIRO_OUT_COEF) && ost != c->cs) {
-    CK(hipStreamWaitEvent(c->cs, c->batch_end[area], 0));
+    CK(hipStreamWaitEvent(c->cs, c->batch_end[l.area], 0));
   }
   // outputs for the host entropy stage: with the feed, the precode's last
   // kernel (k_feed_copy) has written each frame's feed, block table and
   // timeout words into its mapped pinned stage; the coefficient planes (and,
   // without the feed, the table and timeout words) go D2H on the copy stream
-  for (int i = 0; i < e.nframes; i++) {
-    const int slot = c->pend[i].slot;
+  for (int i = 0; i < l.e.nframes; i++) {
+    const int slot = c->pend[i].f.slot;
     Stage& s = c->st[slot];
-    if (c->pend[i].decode) {  // the decoder's output is the slot (decode_frame converts it)
+    if (c->pend[i].f.decode) {  // the decoder's output is the slot (decode_frame converts it)
       s.launched = true;
       continue;
     }
@@ -857,8 +914,29 @@ int flush(cairo_ctx* c) {
     }
     s.launched = true;
   }
-  c->last_slot = last;
-  c->last_epoch = last_epoch;
+  return kSuccess;
+}
+
+// Launch the pending batch: the steps above, in the order their comments give
+// reasons for.
+int flush(cairo_ctx* c) {
+  if (c->npend == 0) return kSuccess;
+  CK(hipSetDevice(c->device));
+  Launch l;
+  int r = plan_launch(c, l);  // pool split and queue choice
+  // inputs
+  if (!r) r = enqueue_uploads(c, l);
+  if (!r) r = enqueue_prepass(c, l, Pending::kScaled, &Pending::scale, launch_scale_batch);
+  if (!r) r = enqueue_prepass(c, l, Pending::kTensor, &Pending::tens, launch_tensor_pack_batch);
+  if (!r) r = enqueue_convert(c, l);
+  // engine and batch wait
+  if (!r) r = enqueue_engine(c, l);
+  // outputs
+  if (!r) r = enqueue_results(c, l);
+  if (!r) r = enqueue_copies(c, l);
+  if (r) return r;
+  c->last_slot = c->pend[c->npend - 1].f.slot;
+  c->last_epoch = c->pend[c->npend - 1].f.epoch;
   c->npend = 0;
   c->launched_cv.notify_all();
   return kSuccess;
@@ -951,9 +1029,151 @@ int sync_all(cairo_ctx* c) {
   return kSuccess;
 }
 
+// Whether [p, p + bytes) is device memory of the context's GPU, inside one
+// allocation (bytes 0: only where p points is asked): a wrong pitch or stride is
+// refused here, not found as an access past the buffer.  Says why not, for `who`.
+bool device_span(const cairo_ctx* c, const void* p, uint64_t bytes, const char* who) {
+  hipPointerAttribute_t pa;
+  if (hipPointerGetAttributes(&pa, p) != hipSuccess || pa.type != hipMemoryTypeDevice || pa.device != c->device) {
+    (void)hipGetLastError();
+    fprintf(stderr, "[cairo_amd] %s: %p is not device memory of device %d (host memory is not taken here)\n", who, p,
+            c->device);
+    return false;
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (bytes && (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess ||
+                (uint64_t)((const uint8_t*)p - (const uint8_t*)base) + bytes > (uint64_t)size)) {
+    (void)hipGetLastError();
+    fprintf(stderr, "[cairo_amd] %s: the span of %llu bytes at %p does not fit its allocation on device %d\n", who,
+            (unsigned long long)bytes, p, c->device);
+    return false;
+  }
+  return true;
+}
+
+// A host frame into its staging slot (mu held).  One context uploads it now,
+// beside the launches in flight; a group member at its launch, on the launch
+// stream (its queue budget, join_group): the caller keeps it valid until wait.
+int stage_host_frame(cairo_ctx* c, Stage& s, Pending& p, const uint8_t* rgb) {
+  p.f.host_rgb = rgb;
+  if (c->gsize > 1) return kSuccess;
+  // The staging buffer's previous frame may still wait for its conversion (a
+  // caller may release a ticket without waiting for it): the upload waits for
+  // the launch that converts it (rgb_read).  With feed outputs only, the copy
+  // stream carries nothing else once a context uploads (flush then keeps the
+  // feed copies on the launch stream), so the uploads use it: on a stream of
+  // their own they ran at 12.3 GB/s instead of 19.1 (bench.py host_rgb, 4K;
+  // GPU_MAX_HW_QUEUES is 4 by default: a fifth stream shares a hardware queue
+  // with one of the others).  With the coefficient planes' D2H copies queued
+  // on the copy stream, they get a stream of their own.
+  c->host_uploads = true;
+  hipStream_t up = c->cs;
+  if (c->outputs & CAIRO_OUT_COEF) {
+    if (!c->us) CK(hipStreamCreateWithFlags(&c->us, hipStreamNonBlocking));
+    up = c->us;
+  }
+  if (!c->up_last) CK(hipEventCreateWithFlags(&c->up_last, hipEventDisableTiming));
+  if (s.rgb_pending) {
+    CK(hipStreamWaitEvent(up, s.rgb_read, 0));
+    s.rgb_pending = false;
+  }
+  // packed tight into the slot (3 * w * h bytes for RGB24)
+  const int r = copy_frame(c, const_cast<uint8_t*>(p.f.rgb), const_cast<uint8_t*>(rgb), true, p.fmt, p.hpitch, up);
+  if (r) return r;
+  CK(hipEventRecord(c->up_last, up));
+  c->up_pending = true;
+  p.f.host_rgb = nullptr;
+  return kSuccess;
+}
+
+// A plane set into a staging slot's frame buffer, tight: RGB888 through
+// k_yuv_to_rgb (kSinkRgb888, as cairo_ctx_decode_frame ever did), or any
+// CAIRO_FMT_* through k_planes_to_fmt.  Asynchronous on st.
+int stage_planes(const cairo_ctx* c, const PlaneSet& p, int slot, int fmt, hipStream_t st) {
+  if (fmt == kSinkRgb888)
+    return fail(launch_yuv_to_rgb(p, (int)c->wa, (int)c->w, (int)c->h, slot_rgb(c, slot), st), "launch_yuv_to_rgb");
+  uint32_t tight = 0;
+  if (cairo_frame_layout(fmt, c->w, c->h, 0, nullptr, &tight) != kSuccess) return kInvalidArg;
+  return fail(launch_planes_to_fmt(p, (int)c->wa, (int)c->w, (int)c->h, fmt, tight, slot_rgb(c, slot), c->out_col, st),
+              "launch_planes_to_fmt");
+}
+
+// The frame staged tight in a slot, out to its sink: through the output map
+// into the sink's device tensor (the slot holds RGB888; the caller checked the
+// span), or to the caller's host frame (copy_frame).  Asynchronous on st.
+int write_staged(const cairo_ctx* c, int slot, const FrameSink& out, hipStream_t st) {
+  uint8_t* staged = slot_rgb(c, slot);
+  if (out.tensor) {
+    TensorArgs ta;
+    ta.w = (int)c->w, ta.h = (int)c->h, ta.nframes = 1, ta.reserved = 0;
+    ta.f[0] = TensorFrame{out.base, staged, *out.tensor};
+    return fail(launch_tensor_unpack(ta, st), "launch_tensor_unpack");
+  }
+  return copy_frame(c, staged, out.base, false, out.fmt, out.pitch, st);
+}
+
 }  // namespace
 
 extern "C" {
+
+// cairo_ctx_create_ex: the streams and every device buffer of a context whose
+// geometry is set.
+static int alloc_device(cairo_ctx* c) {
+  CK(hipSetDevice(c->device));
+  {  // engine pools per launch: half of the resident workgroup slots, split
+     // between helpers and row coders at submit
+    int cus = 0, per_cu = 0;
+    CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    CK(engine_blocks_per_cu(&per_cu));
+    c->max_rows = std::max(1, cus * per_cu / 4);
+  }
+  CK(hipStreamCreateWithFlags(&c->ks, hipStreamNonBlocking));
+  CK(hipStreamCreateWithFlags(&c->ks2, hipStreamNonBlocking));
+  CK(hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking));
+  const size_t S = (size_t)c->stages;
+  CK(hipMalloc(&c->src, c->plane_elems * 2 * S));
+  CK(alloc_coef(c, false, c->coef, &c->coef_chunks, &c->coef_per));
+  CK(hipMalloc(&c->ring_buf, c->plane_elems * 2 * c->ring));
+  c->ring_slots = (int)c->ring;
+  CK(hipMalloc(&c->table, c->mbs * sizeof(BlockDesc) * S));
+  CK(hipMalloc(&c->idesc, c->nref * c->mbs * sizeof(BlockDesc) * S));
+  CK(hipMalloc(&c->gran, c->mbs * kGranuleStride * sizeof(uint64_t) * S));
+  CK(hipMalloc(&c->rgb, (size_t)c->w * c->h * 3 * S));
+  CK(hipMalloc(&c->sync, c->sync_words * sizeof(int32_t) * kSyncAreas));
+  CK(hipMalloc(&c->progress, (size_t)c->hmb * sizeof(uint64_t) * S));
+  CK(hipMalloc(&c->sticky, TimeoutInfo::kWords * sizeof(int32_t)));
+  CK(hipMemset(c->sticky, 0, TimeoutInfo::kWords * sizeof(int32_t)));
+  CK(hipHostMalloc(&c->fdesc_host, sizeof(FrameArgs) * kLaunchSlots * kMaxBatch, hipHostMallocMapped));
+  CK(hipHostGetDevicePointer((void**)&c->fdesc_host_dev, c->fdesc_host, 0));
+  CK(hipMalloc(&c->fdesc, sizeof(FrameArgs) * kLaunchSlots * kMaxBatch));
+  // (frame, row) task order of the engine pools, for every batch size
+  CK(hipMalloc(&c->order, OrderBlock::words((int)c->hmb) * sizeof(int32_t)));
+  return upload_orders(c, kOrderSlope);
+}
+
+// cairo_ctx_create_ex: the stages' pinned host buffers, and the events.
+static int alloc_records(cairo_ctx* c) {
+  for (auto& s : c->st) {
+    CK(hipHostMalloc(&s.table, c->mbs * sizeof(BlockDesc), hipHostMallocMapped));
+    CK(hipHostMalloc(&s.coef, c->plane_elems * 2, hipHostMallocDefault));
+    CK(hipHostMalloc(&s.err, TimeoutInfo::kWords * sizeof(int32_t), hipHostMallocMapped));
+    memset(s.err, 0, TimeoutInfo::kWords * sizeof(int32_t));
+    CK(hipHostGetDevicePointer((void**)&s.table_dev, s.table, 0));
+    CK(hipHostGetDevicePointer((void**)&s.err_dev, s.err, 0));
+    CK(hipEventCreateWithFlags(&s.d2h_done, hipEventDisableTiming));
+    CK(hipEventCreateWithFlags(&s.rgb_read, hipEventDisableTiming));
+  }
+  for (auto& t : c->tb)
+    for (auto& e : t.ev) CK(hipEventCreate(&e));
+  CK(hipEventCreateWithFlags(&c->engine_done, hipEventDisableTiming));
+  CK(hipEventCreate(&c->t_base));
+  for (auto& ev : c->batch_end) CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  for (auto& ev : c->batch_ready) CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  for (auto& ev : c->pre_done) CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  for (auto& ev : c->fdesc_done) CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  return kSuccess;
+}
 
 int cairo_ctx_create(uint32_t width, uint32_t height, uint32_t ring, int device, cairo_ctx** out) {
   return cairo_ctx_create_ex(width, height, ring, device, kDefaultStages, out);
@@ -989,70 +1209,9 @@ int cairo_ctx_create_ex(uint32_t width, uint32_t height, uint32_t ring, int devi
   c->batch_max = std::min(default_batch(c->mbs), stages / 2);
   c->nref = ring > 1 ? ring - 1 : 1;
   c->sync_words = (size_t)SyncLayout::words((int)c->hmb, (int)(c->wmb + 3) / 4);
-  int r = kSuccess;
-#define TRY(x)                         \
-  do {                                 \
-    r = fail((x), #x);                 \
-    if (r != kSuccess) {               \
-      free_ctx(c);                     \
-      return r;                        \
-    }                                  \
-  } while (0)
-  TRY(hipSetDevice(device));
-  {  // engine pools per launch: half of the resident workgroup slots, split
-     // between helpers and row coders at submit
-    int cus = 0, per_cu = 0;
-    TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    TRY(engine_blocks_per_cu(&per_cu));
-    c->max_rows = std::max(1, cus * per_cu / 4);
-  }
-  TRY(hipStreamCreateWithFlags(&c->ks, hipStreamNonBlocking));
-  TRY(hipStreamCreateWithFlags(&c->ks2, hipStreamNonBlocking));
-  TRY(hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking));
-  const size_t S = (size_t)stages;
-  TRY(hipMalloc(&c->src, c->plane_elems * 2 * S));
-  TRY(alloc_coef(c, false, c->coef, &c->coef_chunks, &c->coef_per));
-  TRY(hipMalloc(&c->ring_buf, c->plane_elems * 2 * ring));
-  c->ring_slots = (int)ring;
-  TRY(hipMalloc(&c->table, c->mbs * sizeof(BlockDesc) * S));
-  TRY(hipMalloc(&c->idesc, c->nref * c->mbs * sizeof(BlockDesc) * S));
-  TRY(hipMalloc(&c->gran, c->mbs * kGranuleStride * sizeof(uint64_t) * S));
-  TRY(hipMalloc(&c->rgb, (size_t)width * height * 3 * S));
-  TRY(hipMalloc(&c->sync, c->sync_words * sizeof(int32_t) * kSyncAreas));
-  TRY(hipMalloc(&c->progress, (size_t)c->hmb * sizeof(uint64_t) * S));
-  TRY(hipMalloc(&c->sticky, TimeoutInfo::kWords * sizeof(int32_t)));
-  TRY(hipMemset(c->sticky, 0, TimeoutInfo::kWords * sizeof(int32_t)));
-  {  // (frame, row) task order of the engine pools, for every batch size
-    TRY(hipHostMalloc(&c->fdesc_host, sizeof(FrameArgs) * kLaunchSlots * kMaxBatch, hipHostMallocMapped));
-    TRY(hipHostGetDevicePointer((void**)&c->fdesc_host_dev, c->fdesc_host, 0));
-    TRY(hipMalloc(&c->fdesc, sizeof(FrameArgs) * kLaunchSlots * kMaxBatch));
-    TRY(hipMalloc(&c->order, OrderBlock::words((int)c->hmb) * sizeof(int32_t)));
-    r = upload_orders(c, kOrderSlope);
-    if (r != kSuccess) {
-      free_ctx(c);
-      return r;
-    }
-  }
-  for (auto& s : c->st) {
-    TRY(hipHostMalloc(&s.table, c->mbs * sizeof(BlockDesc), hipHostMallocMapped));
-    TRY(hipHostMalloc(&s.coef, c->plane_elems * 2, hipHostMallocDefault));
-    TRY(hipHostMalloc(&s.err, TimeoutInfo::kWords * sizeof(int32_t), hipHostMallocMapped));
-    memset(s.err, 0, TimeoutInfo::kWords * sizeof(int32_t));
-    TRY(hipHostGetDevicePointer((void**)&s.table_dev, s.table, 0));
-    TRY(hipHostGetDevicePointer((void**)&s.err_dev, s.err, 0));
-    TRY(hipEventCreateWithFlags(&s.d2h_done, hipEventDisableTiming));
-    TRY(hipEventCreateWithFlags(&s.rgb_read, hipEventDisableTiming));
-  }
-  for (auto& t : c->tb)
-    for (auto& e : t.ev) TRY(hipEventCreate(&e));
-  TRY(hipEventCreateWithFlags(&c->engine_done, hipEventDisableTiming));
-  TRY(hipEventCreate(&c->t_base));
-  for (auto& ev : c->batch_end) TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  for (auto& ev : c->batch_ready) TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  for (auto& ev : c->pre_done) TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  for (auto& ev : c->fdesc_done) TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-#undef TRY
-  r = zero_state(c);
+  int r = alloc_device(c);
+  if (r == kSuccess) r = alloc_records(c);
+  if (r == kSuccess) r = zero_state(c);
   if (r != kSuccess) {
     free_ctx(c);
     return r;
@@ -1190,182 +1349,28 @@ int cairo_ctx_busy_intervals(cairo_ctx* c, double* out, int cap, int* n) {
   return kSuccess;
 }
 
-// cairo_ctx_submit (RGB24, tight) and cairo_ctx_submit_fmt.  check_range: an
-// on-device frame must lie, with all its bytes, inside one allocation.
-// With a source description (cairo_ctx_submit_scaled) rgb is a device frame of
-// the source's size and pitch is the source's: the frame is recorded as a
-// device frame whose f.rgb is its staging slot, tight, which the launch's
-// k_scale_batch fills from the source (flush).
-// With a tensor description (cairo_ctx_submit_tensor) rgb is element (0, 0, 0)
-// of a device tensor: recorded the same way, tight RGB24 in the slot, which the
-// launch's k_tensor_pack_batch fills.
-static int submit_frame(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch, bool check_range,
-                        uint32_t index, uint32_t type, uint32_t quality, int* ticket,
-                        const cairo_source* scaled = nullptr, const cairo_tensor* tens = nullptr) {
-  if (!c || !rgb || !ticket || quality < 1 || quality > 31 || type > 1) return kInvalidArg;
-  uint64_t frame_bytes = 0;
-  uint32_t tight = 0;
-  ScaleFrame plan{};
-  if (tens) {  // frame_bytes: the span
-    if (tensor_check(tens, rgb, c->w, c->h, &frame_bytes) != kSuccess) return kInvalidArg;
-    tight = 3 * c->w;
-  } else if (scaled) {
-    // (the scaler's grid has a row per plane row: at most 65535)
-    if (2ull * c->h > 65535 || scale_plan(fmt, pitch, scaled, c->w, c->h, rgb, nullptr, &plan) != kSuccess ||
-        cairo_frame_layout(fmt, scaled->width, scaled->height, pitch, &frame_bytes, nullptr) != kSuccess ||
-        cairo_frame_layout(fmt, c->w, c->h, 0, nullptr, &tight) != kSuccess)
-      return kInvalidArg;
-  } else if (cairo_frame_layout(fmt, c->w, c->h, pitch, &frame_bytes, &tight) != kSuccess) {
-    return kInvalidArg;
-  }
-  std::lock_guard<std::mutex> lk(c->mu);
-  CK(hipSetDevice(c->device));
-  const int t = c->next_ticket;
-  const int slot = t % c->stages;
-  Stage& s = c->st[slot];
-  if (s.busy) {
-    fprintf(stderr, "[cairo_amd] staging slot of ticket %d not released\n", s.ticket);
-    return kInvalidResource;
-  }
-  if (rgb_on_device) {  // the kernels read it: it must be device memory of this context's GPU
-    hipPointerAttribute_t pa;
-    if (hipPointerGetAttributes(&pa, rgb) != hipSuccess || pa.type != hipMemoryTypeDevice || pa.device != c->device) {
-      (void)hipGetLastError();
-      if (tens)
-        fprintf(stderr, "[cairo_amd] submit_tensor: %p is not device memory of device %d (a host tensor is not taken: "
-                "the 3*W*H staging slot cannot stage a float frame)\n", (const void*)rgb, c->device);
-      else if (scaled)
-        fprintf(stderr, "[cairo_amd] submit_scaled: the source %p is not device memory of device %d (a host source is "
-                "not scaled: upload it once and submit the device frame)\n", (const void*)rgb, c->device);
-      else
-        fprintf(stderr, "[cairo_amd] submit: rgb_on_device but %p is not device memory of device %d\n",
-                (const void*)rgb, c->device);
-      return kInvalidArg;
-    }
-    if (check_range) {  // a wrong pitch is refused here, not found as a read past the buffer
-      hipDeviceptr_t base = nullptr;
-      size_t size = 0;
-      if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)rgb) != hipSuccess ||
-          (uint64_t)((const uint8_t*)rgb - (const uint8_t*)base) + frame_bytes > (uint64_t)size) {
-        (void)hipGetLastError();
-        if (tens)
-          fprintf(stderr, "[cairo_amd] submit_tensor: the tensor's span (%llu bytes) at %p does not fit its allocation\n",
-                  (unsigned long long)frame_bytes, (const void*)rgb);
-        else
-          fprintf(stderr, "[cairo_amd] submit: a format %d frame with pitch %u (%llu bytes) at %p does not fit its allocation\n",
-                  fmt, scaled ? plan.pitch : (pitch ? pitch : tight), (unsigned long long)frame_bytes, (const void*)rgb);
-        return kInvalidArg;
-      }
-    }
-  }
-  FrameDesc& f = c->pend[c->npend];
-  c->pend_fmt[c->npend] = (uint8_t)fmt;
-  c->pend_pitch[c->npend] = rgb_on_device && pitch && !scaled && !tens ? pitch : tight;  // a host frame is staged tight
-  c->pend_hpitch[c->npend] = pitch;
-  c->pend_col[c->npend] = fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_NV12 ? (uint8_t)c->in_col : 0;
-  c->pend_scaled[c->npend] = scaled != nullptr;
-  c->pend_tensor[c->npend] = tens != nullptr;
-  if (scaled) {  // scaled into the slot at launch, tight
-    f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
-    f.host_rgb = nullptr;
-    plan.dst = const_cast<uint8_t*>(f.rgb);
-    c->pend_scale[c->npend] = plan;
-  } else if (tens) {  // packed into the slot at launch, tight RGB24
-    f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
-    f.host_rgb = nullptr;
-    TensorFrame& tf = c->pend_tens[c->npend];
-    tf.tensor = const_cast<uint8_t*>(rgb);
-    tf.rgb = const_cast<uint8_t*>(f.rgb);
-    tf.d = *tens;
-  } else if (rgb_on_device) {
-    f.rgb = rgb;
-    f.host_rgb = nullptr;
-  } else {  // the caller keeps it valid until wait
-    f.rgb = c->rgb + (size_t)slot * c->w * c->h * 3;
-    f.host_rgb = rgb;
-    if (c->gsize == 1) {
-      // Uploaded now, beside the launches in flight.  The staging buffer's
-      // previous frame may still wait for its conversion (a caller may release
-      // a ticket without waiting for it): the upload waits for the launch that
-      // converts it (rgb_read).  With feed outputs only, the copy stream
-      // carries nothing else once a context uploads (flush then keeps the feed
-      // copies on the launch stream), so the uploads use it: on a stream of
-      // their own they ran at 12.3 GB/s instead of 19.1 (bench.py host_rgb,
-      // 4K; GPU_MAX_HW_QUEUES is 4 by default: a fifth stream shares a
-      // hardware queue with one of the others).  With the coefficient planes' D2H
-      // copies queued on the copy stream, they get a stream of their own.
-      c->host_uploads = true;
-      hipStream_t up = c->cs;
-      if (c->outputs & CAIRO_OUT_COEF) {
-        if (!c->us) CK(hipStreamCreateWithFlags(&c->us, hipStreamNonBlocking));
-        up = c->us;
-      }
-      if (!c->up_last) CK(hipEventCreateWithFlags(&c->up_last, hipEventDisableTiming));
-      if (s.rgb_pending) {
-        CK(hipStreamWaitEvent(up, s.rgb_read, 0));
-        s.rgb_pending = false;
-      }
-      {  // packed tight into the slot, frame_bytes long (3 * w * h for RGB24)
-        const int ru = upload_frame(c, const_cast<uint8_t*>(f.rgb), rgb, fmt, pitch, up);
-        if (ru) return ru;
-      }
-      CK(hipEventRecord(c->up_last, up));
-      c->up_pending = true;
-      f.host_rgb = nullptr;
-    }
-  }
-  if (c->gsize > 1 && (long)index != (long)(t - c->gbase) * c->gsize + c->grank) {
-    fprintf(stderr, "[cairo_amd] group member %d of %d: frame %u out of turn\n", c->grank, c->gsize, index);
-    return kInvalidArg;
-  }
-  f.index = (int)index;
-  f.inter = type == 1 ? 1 : 0;
-  f.quality = (int)quality;
-  // granule tag; frames of a stream have consecutive epochs (a group numbers
-  // them by stream index)
-  f.epoch = c->gsize > 1 ? index + 1 : ++c->epoch;
-  f.slot = slot;
-  f.member = c->grank;
-  f.decode = 0;  // decode_frame never leaves a decode frame pending
-  f.host_table = nullptr;
-  f.host_coef = nullptr;
-  frame_links(c, f, t);
-  c->npend++;
-  s.busy = true;
-  s.launched = false;
-  s.waited = false;
-  s.mflags = c->metrics;
-  s.ticket = t;
-  s.index = index;
-  s.type = type;
-  s.quality = quality;
-  c->next_ticket++;
-  *ticket = t;
-  if (c->npend >= c->batch_max) return flush(c);
-  return kSuccess;
-}
-
 int cairo_ctx_submit(cairo_ctx* c, const uint8_t* rgb, int rgb_on_device, uint32_t index,
                      uint32_t type, uint32_t quality, int* ticket) {
-  return submit_frame(c, rgb, rgb_on_device, CAIRO_FMT_RGB24, 0, false, index, type, quality, ticket);
+  return submit_frame(c, {rgb, rgb_on_device, CAIRO_FMT_RGB24, 0, false, nullptr, nullptr}, index, type, quality,
+                      ticket);
 }
 
 int cairo_ctx_submit_fmt(cairo_ctx* c, const uint8_t* frame, int on_device, int fmt, uint32_t pitch, uint32_t index,
                          uint32_t type, uint32_t quality, int* ticket) {
-  return submit_frame(c, frame, on_device, fmt, pitch, true, index, type, quality, ticket);
+  return submit_frame(c, {frame, on_device, fmt, pitch, true, nullptr, nullptr}, index, type, quality, ticket);
 }
 
 int cairo_ctx_submit_scaled(cairo_ctx* c, const uint8_t* frame, int fmt, uint32_t pitch, const cairo_source* src,
                             uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (!src) return kInvalidArg;
-  return submit_frame(c, frame, 1, fmt, pitch, true, index, type, quality, ticket, src);
+  return submit_frame(c, {frame, 1, fmt, pitch, true, src, nullptr}, index, type, quality, ticket);
 }
 
 int cairo_ctx_submit_tensor(cairo_ctx* c, const void* base, const cairo_tensor* desc, uint32_t index, uint32_t type,
                             uint32_t quality, int* ticket) {
   if (!desc) return kInvalidArg;
-  return submit_frame(c, (const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, index, type, quality, ticket, nullptr,
-                      desc);
+  return submit_frame(c, {(const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, nullptr, desc}, index, type, quality,
+                      ticket);
 }
 
 static const char* timeout_kind_name(int k) {
@@ -1489,155 +1494,21 @@ int cairo_ctx_wait(cairo_ctx* c, int ticket, cairo_frame_result* out) {
   return frame_result(c, s, out);
 }
 
-// A frame staged tight on the device (frame_bytes long, rows of `tight` bytes;
-// fmt < 0: RGB888) to the caller's host buffer: one copy when that is tight
-// too, else row by row per plane, so the caller's pitch padding keeps its
-// bytes.  Asynchronous on st.
-static int download_frame(const cairo_ctx* c, uint8_t* dst, const uint8_t* staged, int fmt, uint32_t pitch,
-                          uint32_t tight, uint64_t frame_bytes, hipStream_t st) {
-  if (fmt < 0 || !pitch || pitch == tight) {
-    CK(hipMemcpyAsync(dst, staged, (size_t)frame_bytes, hipMemcpyDeviceToHost, st));
-    return kSuccess;
-  }
-  const size_t w = c->w, h = c->h;
-  CK(hipMemcpy2DAsync(dst, pitch, staged, tight, tight, h, hipMemcpyDeviceToHost, st));
-  uint8_t* dc = dst + (size_t)pitch * h;
-  const uint8_t* sc = staged + w * h;
-  if (fmt == CAIRO_FMT_I420) {
-    const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
-    CK(hipMemcpy2DAsync(dc, cp, sc, cw, cw, ch, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpy2DAsync(dc + cp * ch, cp, sc + cw * ch, cw, cw, ch, hipMemcpyDeviceToHost, st));
-  } else if (fmt == CAIRO_FMT_NV12) {
-    CK(hipMemcpy2DAsync(dc, pitch, sc, w, w, h / 2, hipMemcpyDeviceToHost, st));
-  }
-  return kSuccess;
-}
-
-// Whether [p, p + bytes) is device memory of the context's GPU inside one
-// allocation (a tensor the unpack kernel is about to write).
-static bool device_span(const cairo_ctx* c, const void* p, uint64_t bytes, const char* who) {
-  hipPointerAttribute_t pa;
-  if (hipPointerGetAttributes(&pa, p) != hipSuccess || pa.type != hipMemoryTypeDevice || pa.device != c->device) {
-    (void)hipGetLastError();
-    fprintf(stderr, "[cairo_amd] %s: %p is not device memory of device %d (a host tensor is not taken)\n", who, p,
-            c->device);
-    return false;
-  }
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess ||
-      (uint64_t)((const uint8_t*)p - (const uint8_t*)base) + bytes > (uint64_t)size) {
-    (void)hipGetLastError();
-    fprintf(stderr, "[cairo_amd] %s: the tensor's span (%llu bytes) at %p does not fit its allocation\n", who,
-            (unsigned long long)bytes, p);
-    return false;
-  }
-  return true;
-}
-
-// The tight RGB888 frame staged at `staged` through the output map into the
-// tensor at tbase (checked by the caller).  Asynchronous on st.
-static int unpack_to_tensor(const cairo_ctx* c, uint8_t* staged, void* tbase, const cairo_tensor* tens,
-                            hipStream_t st) {
-  TensorArgs ta;
-  ta.w = (int)c->w, ta.h = (int)c->h, ta.nframes = 1, ta.reserved = 0;
-  ta.f[0].tensor = (uint8_t*)tbase, ta.f[0].rgb = staged, ta.f[0].d = *tens;
-  return fail(launch_tensor_unpack(ta, st), "launch_tensor_unpack");
-}
-
-// cairo_ctx_decode_frame (fmt < 0: RGB888 through k_yuv_to_rgb, as ever) and
-// cairo_ctx_decode_frame_fmt (k_planes_to_fmt, tight in the staging slot; the
-// D2H copy is 2D per plane when the caller's frame is pitched).
-// With a tensor description (cairo_ctx_decode_frame_tensor) rgb is element
-// (0, 0, 0) of a device tensor: RGB888 into the slot as for fmt < 0, then
-// k_tensor_unpack into the tensor instead of the download.
-static int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, int fmt,
-                        uint32_t pitch, uint8_t* rgb, const cairo_tensor* tens = nullptr) {
-  if (!c || !table || !coef || !rgb) return kInvalidArg;
-  uint64_t frame_bytes = (uint64_t)c->w * c->h * 3;
-  uint32_t tight = 3 * c->w;
-  uint64_t span = 0;
-  if (tens && tensor_check(tens, rgb, c->w, c->h, &span) != kSuccess) return kInvalidArg;
-  if (fmt >= 0 && cairo_frame_layout(fmt, c->w, c->h, pitch, nullptr, &tight) != kSuccess) return kInvalidArg;
-  if (fmt >= 0) (void)cairo_frame_layout(fmt, c->w, c->h, 0, &frame_bytes, nullptr);  // as staged: tight
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (c->gsize > 1) return kInvalidResource;
-  CK(hipSetDevice(c->device));
-  if (tens && !device_span(c, rgb, span, "decode_frame_tensor")) return kInvalidArg;
-  int r = flush(c);  // encode frames still pending go first, in their own launch
-  if (r) return r;
-  const int t = c->next_ticket, slot = t % c->stages;
-  Stage& s = c->st[slot];
-  if (s.busy) {
-    fprintf(stderr, "[cairo_amd] staging slot of ticket %d not released\n", s.ticket);
-    return kInvalidResource;
-  }
-  FrameDesc& f = c->pend[0];
-  memset(&f, 0, sizeof(f));
-  f.index = (int)index;
-  f.inter = 1;
-  f.quality = 1;
-  f.epoch = ++c->epoch;
-  f.slot = slot;
-  f.decode = 1;
-  frame_links(c, f, t);
-  f.host_table = reinterpret_cast<const BlockDesc*>(table);
-  f.host_coef = coef;
-  c->pend_scaled[0] = false;
-  c->pend_tensor[0] = false;
-  c->npend = 1;
-  s.busy = true;
-  s.launched = false;
-  s.waited = false;
-  s.mflags = 0;
-  s.ticket = t;
-  s.index = index;
-  s.type = 1;
-  s.quality = 0;
-  c->next_ticket++;
-  const long long b = c->batches;  // the launch flush() is about to make
-  r = flush(c);
-  if (r == kSuccess) {
-    hipStream_t st = (b & 1) ? c->ks2 : c->ks;
-    uint8_t* drgb = c->rgb + (size_t)slot * c->w * c->h * 3;
-    const PlaneSet recon = slot_planes(c->ring_buf, c, (int)(index % c->ring));
-    if (fmt < 0)
-      r = fail(launch_yuv_to_rgb(recon, (int)c->wa, (int)c->w, (int)c->h, drgb, st), "launch_yuv_to_rgb");
-    else
-      r = fail(launch_planes_to_fmt(recon, (int)c->wa, (int)c->w, (int)c->h, fmt, tight, drgb, c->out_col, st),
-               "launch_planes_to_fmt");
-    if (r == kSuccess)
-      r = fail(hipMemcpyAsync(s.err, c->sticky, TimeoutInfo::kWords * sizeof(int32_t), hipMemcpyDeviceToHost, st),
-               "hipMemcpyAsync");
-    if (r == kSuccess && tens)
-      r = unpack_to_tensor(c, drgb, rgb, tens, st);
-    else if (r == kSuccess)
-      r = download_frame(c, rgb, drgb, fmt, pitch, tight, frame_bytes, st);
-    if (r == kSuccess) r = fail(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (r == kSuccess && s.err[TimeoutInfo::kKind]) {
-      report_timeout_host(c, s.err, index, st);  // (mu held: the launch stream, idle now)
-      r = kHardwareFail;
-    }
-  }
-  s.busy = false;
-  return r;
-}
-
 int cairo_ctx_decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index,
                            uint8_t* rgb) {
-  return decode_frame(c, table, coef, index, -1, 0, rgb);
+  return decode_frame(c, table, coef, index, {rgb, kSinkRgb888, 0, nullptr});
 }
 
 int cairo_ctx_decode_frame_fmt(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, int fmt,
                                uint32_t pitch, uint8_t* out) {
   if (fmt < 0) return kInvalidArg;
-  return decode_frame(c, table, coef, index, fmt, pitch, out);
+  return decode_frame(c, table, coef, index, {out, fmt, pitch, nullptr});
 }
 
 int cairo_ctx_decode_frame_tensor(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, void* base,
                                   const cairo_tensor* desc) {
   if (!desc) return kInvalidArg;
-  return decode_frame(c, table, coef, index, -1, 0, (uint8_t*)base, desc);
+  return decode_frame(c, table, coef, index, {(uint8_t*)base, kSinkRgb888, 0, desc});
 }
 
 static bool color_known(int range, int matrix) {
@@ -1645,19 +1516,14 @@ static bool color_known(int range, int matrix) {
          (matrix == CAIRO_MATRIX_BT601 || matrix == CAIRO_MATRIX_BT709);
 }
 
-int cairo_ctx_set_input_color(cairo_ctx* c, int range, int matrix) {
+static int set_color(cairo_ctx* c, int cairo_ctx::*col, int range, int matrix) {
   if (!c || !color_known(range, matrix)) return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
-  c->in_col = color_index(range, matrix);  // frames already submitted keep theirs (pend_col)
+  c->*col = color_index(range, matrix);  // frames already submitted keep theirs (Pending::col)
   return kSuccess;
 }
-
-int cairo_ctx_set_output_color(cairo_ctx* c, int range, int matrix) {
-  if (!c || !color_known(range, matrix)) return kInvalidArg;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->out_col = color_index(range, matrix);
-  return kSuccess;
-}
+int cairo_ctx_set_input_color(cairo_ctx* c, int r, int m) { return set_color(c, &cairo_ctx::in_col, r, m); }
+int cairo_ctx_set_output_color(cairo_ctx* c, int r, int m) { return set_color(c, &cairo_ctx::out_col, r, m); }
 
 int cairo_ctx_max_workgroups(const cairo_ctx* c) { return c ? c->max_rows : 0; }
 
@@ -1798,26 +1664,26 @@ int cairo_ctx_fetch_recon_planes(cairo_ctx* c, int ticket, int16_t* y, int16_t* 
   return kSuccess;
 }
 
-int cairo_ctx_fetch_recon(cairo_ctx* c, int ticket, int fmt, uint32_t pitch, uint8_t* out) {
-  if (!c || !out) return kInvalidArg;
-  uint64_t frame_bytes = 0;
-  uint32_t tight = 0;
-  if (cairo_frame_layout(fmt, c->w, c->h, pitch, nullptr, &tight) != kSuccess) return kInvalidArg;
-  (void)cairo_frame_layout(fmt, c->w, c->h, 0, &frame_bytes, nullptr);  // as staged: tight
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!kept_stage(c, ticket)) return kInvalidArg;
-  CK(hipSetDevice(c->device));
+// cairo_ctx_fetch_recon and _fetch_recon_tensor (mu held, the sink checked):
+// the ticket's kept planes as out.fmt into the slot's frame buffer -- its own frame
+// was converted before the wait, and the next upload into it follows the
+// ticket's release -- and from there to the sink.
+static int fetch_kept(cairo_ctx* c, int ticket, const FrameSink& out) {
   if (!c->fs) CK(hipStreamCreateWithFlags(&c->fs, hipStreamNonBlocking));
-  // staged in the slot's frame buffer: its own frame was converted before the
-  // wait, and the next upload into it follows the ticket's release
   const int slot = ticket % c->stages;
-  uint8_t* staged = c->rgb + (size_t)slot * c->w * c->h * 3;
-  CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, fmt, tight, staged,
-                          c->out_col, c->fs));
-  const int r = download_frame(c, out, staged, fmt, pitch, tight, frame_bytes, c->fs);
+  int r = stage_planes(c, slot_planes(c->keep, c, slot), slot, out.fmt, c->fs);
+  if (!r) r = write_staged(c, slot, out, c->fs);
   if (r) return r;
   CK(hipStreamSynchronize(c->fs));
   return kSuccess;
+}
+
+int cairo_ctx_fetch_recon(cairo_ctx* c, int ticket, int fmt, uint32_t pitch, uint8_t* out) {
+  if (!c || !out || cairo_frame_layout(fmt, c->w, c->h, pitch, nullptr, nullptr) != kSuccess) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!kept_stage(c, ticket)) return kInvalidArg;
+  CK(hipSetDevice(c->device));
+  return fetch_kept(c, ticket, {out, fmt, pitch, nullptr});
 }
 
 int cairo_ctx_fetch_recon_tensor(cairo_ctx* c, int ticket, void* base, const cairo_tensor* desc) {
@@ -1828,16 +1694,8 @@ int cairo_ctx_fetch_recon_tensor(cairo_ctx* c, int ticket, void* base, const cai
   if (!kept_stage(c, ticket)) return kInvalidArg;
   CK(hipSetDevice(c->device));
   if (!device_span(c, base, span, "fetch_recon_tensor")) return kInvalidArg;
-  if (!c->fs) CK(hipStreamCreateWithFlags(&c->fs, hipStreamNonBlocking));
-  // staged in the slot's frame buffer as tight RGB24, as cairo_ctx_fetch_recon does
-  const int slot = ticket % c->stages;
-  uint8_t* staged = c->rgb + (size_t)slot * c->w * c->h * 3;
-  CK(launch_planes_to_fmt(slot_planes(c->keep, c, slot), (int)c->wa, (int)c->w, (int)c->h, CAIRO_FMT_RGB24, 3 * c->w,
-                          staged, c->out_col, c->fs));
-  const int r = unpack_to_tensor(c, staged, base, desc, c->fs);
-  if (r) return r;
-  CK(hipStreamSynchronize(c->fs));
-  return kSuccess;
+  // tight RGB24 through k_planes_to_fmt, as cairo_ctx_fetch_recon stages it
+  return fetch_kept(c, ticket, {(uint8_t*)base, CAIRO_FMT_RGB24, 0, desc});
 }
 
 int cairo_ctx_flush(cairo_ctx* c) {
@@ -1940,6 +1798,35 @@ int cairo_group_check_queues(int local_members, int hw_queues) {
   return kSuccess;
 }
 
+// cairo_ctx_join_group: another member's buffers as this member addresses them.
+static int map_peer(cairo_ctx* c, cairo_ctx::Peer& q, const cairo_peer& p, bool same_process) {
+  if (p.coef_chunks < 1 || p.coef_chunks > CAIRO_MAX_COEF_CHUNKS || p.coef_chunk_slots < 1 ||
+      (long)p.coef_chunks * p.coef_chunk_slots < p.stages)
+    return kInvalidArg;
+  q.coef_chunks = p.coef_chunks, q.coef_per = p.coef_chunk_slots;
+  if (same_process) {  // the addresses are valid here
+    if (p.device != c->device) {
+      const hipError_t e = hipDeviceEnablePeerAccess(p.device, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(e, "hipDeviceEnablePeerAccess");
+    }
+    q.ring = (int16_t*)(uintptr_t)p.ring_addr;
+    q.progress = (uint64_t*)(uintptr_t)p.progress_addr;
+    for (int k = 0; k < p.coef_chunks; k++) q.coef[k] = (int16_t*)(uintptr_t)p.coef_addr[k];
+    return kSuccess;
+  }
+  // another process: open its IPC handles (peer access over xGMI), each allocation < 1 GiB
+  q.imported = true;
+  auto open = [&](const uint8_t* bytes, void** dst) {
+    hipIpcMemHandle_t h;
+    memcpy(&h, bytes, sizeof(h));
+    return hipIpcOpenMemHandle(dst, h, hipIpcMemLazyEnablePeerAccess);
+  };
+  hipError_t e = open(p.ipc_ring, (void**)&q.ring);
+  if (e == hipSuccess) e = open(p.ipc_progress, (void**)&q.progress);
+  for (int k = 0; e == hipSuccess && k < p.coef_chunks; k++) e = open(p.ipc_coef[k], (void**)&q.coef[k]);
+  return fail(e, "hipIpcOpenMemHandle");
+}
+
 int cairo_ctx_join_group(cairo_ctx* c, int size, int rank, const cairo_peer* peers) {
   if (!c || !peers || size < 1 || size > kMaxGroup || rank < 0 || rank >= size) return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -1974,40 +1861,11 @@ int cairo_ctx_join_group(cairo_ctx* c, int size, int rank, const cairo_peer* pee
       q.coef_chunks = c->coef_chunks, q.coef_per = c->coef_per;
       continue;
     }
-    if (p.coef_chunks < 1 || p.coef_chunks > CAIRO_MAX_COEF_CHUNKS || p.coef_chunk_slots < 1 ||
-        (long)p.coef_chunks * p.coef_chunk_slots < p.stages) {
-      c->gsize = i;
+    const int r = map_peer(c, q, p, p.pid == me);
+    if (r) {  // leave_group closes whatever is open: the members before this one, and its own imports
+      c->gsize = q.imported ? i + 1 : i;
       leave_group(c);
-      return kInvalidArg;
-    }
-    q.coef_chunks = p.coef_chunks, q.coef_per = p.coef_chunk_slots;
-    if (p.pid == me) {  // same process: the addresses are valid here
-      if (p.device != c->device) {
-        const hipError_t e = hipDeviceEnablePeerAccess(p.device, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
-          c->gsize = i;
-          leave_group(c);
-          return fail(e, "hipDeviceEnablePeerAccess");
-        }
-      }
-      q.ring = (int16_t*)(uintptr_t)p.ring_addr;
-      q.progress = (uint64_t*)(uintptr_t)p.progress_addr;
-      for (int k = 0; k < p.coef_chunks; k++) q.coef[k] = (int16_t*)(uintptr_t)p.coef_addr[k];
-    } else {  // another process: open its IPC handles (peer access over xGMI), each allocation < 1 GiB
-      q.imported = true;  // leave_group closes whatever is open
-      auto open = [&](const uint8_t* bytes, void** dst) {
-        hipIpcMemHandle_t h;
-        memcpy(&h, bytes, sizeof(h));
-        return hipIpcOpenMemHandle(dst, h, hipIpcMemLazyEnablePeerAccess);
-      };
-      hipError_t e = open(p.ipc_ring, (void**)&q.ring);
-      if (e == hipSuccess) e = open(p.ipc_progress, (void**)&q.progress);
-      for (int k = 0; e == hipSuccess && k < p.coef_chunks; k++) e = open(p.ipc_coef[k], (void**)&q.coef[k]);
-      if (e != hipSuccess) {
-        c->gsize = i + 1;
-        leave_group(c);
-        return fail(e, "hipIpcOpenMemHandle");
-      }
+      return r;
     }
   }
   c->gsize = size;
@@ -2215,6 +2073,136 @@ int cairo_api_version(void) { return CAIRO_AMD_API_VERSION; }
 }  // extern "C"
 
 namespace cairo {
+
+// Every cairo_ctx_submit* and cairo_stream_submit* call.  A scaled frame
+// (src.base: a device frame of the source's size and pitch) and a tensor frame
+// (src.base: element (0, 0, 0) of a device tensor) are recorded as frames whose
+// f.rgb is their staging slot, tight, which the launch's pre-pass fills from
+// the source (flush: k_scale_batch, k_tensor_pack_batch).
+int submit_frame(cairo_ctx* c, const FrameSource& src, uint32_t index, uint32_t type, uint32_t quality,
+                 int* ticket) {
+  const uint8_t* rgb = src.base;
+  if (!c || !rgb || !ticket || quality < 1 || quality > 31 || type > 1) return kInvalidArg;
+  const Pending::Kind kind = src.tensor ? Pending::kTensor : src.scaled ? Pending::kScaled
+                             : src.on_device ? Pending::kDevice : Pending::kStaged;
+  const char* who = src.tensor ? "submit_tensor" : src.scaled ? "submit_scaled" : "submit";
+  uint64_t frame_bytes = 0;  // of the source as it lies in memory (a tensor's span)
+  uint32_t tight = 3 * c->w;
+  ScaleFrame plan{};
+  if (kind == Pending::kTensor) {
+    if (tensor_check(src.tensor, rgb, c->w, c->h, &frame_bytes) != kSuccess) return kInvalidArg;
+  } else if (kind == Pending::kScaled) {
+    // (the scaler's grid has a row per plane row: at most 65535)
+    const cairo_source& sc = *src.scaled;
+    if (2ull * c->h > 65535 || scale_plan(src.fmt, src.pitch, &sc, c->w, c->h, rgb, nullptr, &plan) != kSuccess ||
+        cairo_frame_layout(src.fmt, sc.width, sc.height, src.pitch, &frame_bytes, nullptr) != kSuccess ||
+        cairo_frame_layout(src.fmt, c->w, c->h, 0, nullptr, &tight) != kSuccess)
+      return kInvalidArg;
+  } else if (cairo_frame_layout(src.fmt, c->w, c->h, src.pitch, &frame_bytes, &tight) != kSuccess) {
+    return kInvalidArg;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  CK(hipSetDevice(c->device));
+  const int t = c->next_ticket, slot = t % c->stages;
+  Stage& s = c->st[slot];
+  if (s.busy) {
+    fprintf(stderr, "[cairo_amd] staging slot of ticket %d not released\n", s.ticket);
+    return kInvalidResource;
+  }
+  if (kind != Pending::kStaged && !device_span(c, rgb, src.check_range ? frame_bytes : 0, who)) return kInvalidArg;
+  if (c->gsize > 1 && (long)index != (long)(t - c->gbase) * c->gsize + c->grank) {
+    fprintf(stderr, "[cairo_amd] group member %d of %d: frame %u out of turn\n", c->grank, c->gsize, index);
+    return kInvalidArg;
+  }
+  Pending& p = c->pend[c->npend];
+  memset(&p, 0, sizeof(p));  // the whole record: nothing is left of the index's previous frame
+  FrameDesc& f = p.f;
+  p.kind = kind;
+  p.fmt = (uint8_t)src.fmt;
+  p.pitch = kind == Pending::kDevice && src.pitch ? src.pitch : tight;  // whatever is staged is staged tight
+  p.hpitch = src.pitch;
+  p.col = src.fmt == CAIRO_FMT_I420 || src.fmt == CAIRO_FMT_NV12 ? (uint8_t)c->in_col : 0;
+  f.rgb = kind == Pending::kDevice ? rgb : slot_rgb(c, slot);
+  if (kind == Pending::kScaled) {
+    plan.dst = slot_rgb(c, slot);
+    p.scale = plan;
+  } else if (kind == Pending::kTensor) {
+    p.tens = TensorFrame{const_cast<uint8_t*>(rgb), slot_rgb(c, slot), *src.tensor};
+  } else if (kind == Pending::kStaged) {
+    const int r = stage_host_frame(c, s, p, rgb);
+    if (r) return r;
+  }
+  f.index = (int)index;
+  f.inter = type == 1 ? 1 : 0;
+  f.quality = (int)quality;
+  // granule tag; frames of a stream have consecutive epochs (a group numbers
+  // them by stream index)
+  f.epoch = c->gsize > 1 ? index + 1 : ++c->epoch;
+  f.slot = slot;
+  f.member = c->grank;
+  frame_links(c, f, t);
+  c->npend++;
+  take_stage(s, t, index, type, quality, c->metrics);
+  c->next_ticket++;
+  *ticket = t;
+  if (c->npend >= c->batch_max) return flush(c);
+  return kSuccess;
+}
+
+// Every cairo_ctx_decode_frame* call: the decode-mode engine reconstructs the
+// frame into its ring slot, stage_planes writes it into the staging slot in
+// the sink's format, write_staged takes it to the caller.
+int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32_t index, const FrameSink& out) {
+  if (!c || !table || !coef || !out.base) return kInvalidArg;
+  uint64_t span = 0;
+  if (out.tensor && tensor_check(out.tensor, out.base, c->w, c->h, &span) != kSuccess) return kInvalidArg;
+  if (out.fmt >= 0 && cairo_frame_layout(out.fmt, c->w, c->h, out.pitch, nullptr, nullptr) != kSuccess)
+    return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->gsize > 1) return kInvalidResource;
+  CK(hipSetDevice(c->device));
+  if (out.tensor && !device_span(c, out.base, span, "decode_frame_tensor")) return kInvalidArg;
+  int r = flush(c);  // encode frames still pending go first, in their own launch
+  if (r) return r;
+  const int t = c->next_ticket, slot = t % c->stages;
+  Stage& s = c->st[slot];
+  if (s.busy) {
+    fprintf(stderr, "[cairo_amd] staging slot of ticket %d not released\n", s.ticket);
+    return kInvalidResource;
+  }
+  Pending& p = c->pend[0];
+  memset(&p, 0, sizeof(p));  // the whole record: a decode frame has no pixel source (kind kStaged, nothing to upload)
+  FrameDesc& f = p.f;
+  f.index = (int)index;
+  f.inter = 1;
+  f.quality = 1;
+  f.epoch = ++c->epoch;
+  f.slot = slot;
+  f.decode = 1;
+  frame_links(c, f, t);
+  f.host_table = reinterpret_cast<const BlockDesc*>(table);
+  f.host_coef = coef;
+  c->npend = 1;
+  take_stage(s, t, index, 1, 0, 0);
+  c->next_ticket++;
+  const long long b = c->batches;  // the launch flush() is about to make
+  r = flush(c);
+  if (r == kSuccess) {
+    hipStream_t st = (b & 1) ? c->ks2 : c->ks;
+    r = stage_planes(c, slot_planes(c->ring_buf, c, (int)(index % c->ring)), slot, out.fmt, st);
+    if (r == kSuccess)
+      r = fail(hipMemcpyAsync(s.err, c->sticky, TimeoutInfo::kWords * sizeof(int32_t), hipMemcpyDeviceToHost, st),
+               "hipMemcpyAsync");
+    if (r == kSuccess) r = write_staged(c, slot, out, st);
+    if (r == kSuccess) r = fail(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (r == kSuccess && s.err[TimeoutInfo::kKind]) {
+      report_timeout_host(c, s.err, index, st);  // (mu held: the launch stream, idle now)
+      r = kHardwareFail;
+    }
+  }
+  s.busy = false;
+  return r;
+}
 
 int ctx_wait_launched(cairo_ctx* c, int ticket, const std::atomic<bool>* stop,
                       cairo_frame_result* out) {

@@ -16,6 +16,7 @@
 #include "../../include/cairo_amd.h"
 #include "../../include/evx1.h"
 #include "evx_defs.h"
+#include "frame_io.h"
 #include "stream_format.h"
 
 namespace cairo {
@@ -58,11 +59,7 @@ class gpu_decoder : public evx1_decoder {
     const uint8_t *tbl = reinterpret_cast<const uint8_t *>(table_);
     // the engine trusts the table: a stream it cannot honour is an error
     if (!cairo_table_check(tbl, wmb_, hmb_, ring_)) return EVX_ERROR_EXECUTION_FAILURE;
-    if (tensor_ ? cairo_ctx_decode_frame_tensor(ctx_, tbl, coef_, f.index, output, &tens_)
-        : fmt_ == CAIRO_FMT_RGB24 && !pitch_
-            ? cairo_ctx_decode_frame(ctx_, tbl, coef_, f.index, static_cast<uint8_t *>(output))
-            : cairo_ctx_decode_frame_fmt(ctx_, tbl, coef_, f.index, fmt_, pitch_, static_cast<uint8_t *>(output)))
-      return EVX_ERROR_EXECUTION_FAILURE;
+    if (cairo::decode_frame(ctx_, tbl, coef_, f.index, out_.sink(output))) return EVX_ERROR_EXECUTION_FAILURE;
     frame_index_++;
     input->empty();
     return EVX_SUCCESS;
@@ -75,31 +72,21 @@ class gpu_decoder : public evx1_decoder {
   }
   // The layout decode() writes its frame in (between frames too).
   evx_status set_output_format(int fmt, uint32 pitch) {
-    // before the first decode the frame size is not known: any even size stands in
-    const uint32 w = initialized_ ? width_ : 2, h = initialized_ ? height_ : 2;
-    if (cairo_frame_layout(fmt, w, h, initialized_ ? pitch : 0, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
-    fmt_ = fmt;
-    pitch_ = pitch;
-    return EVX_SUCCESS;
+    // (the frame size is known once initialised; clear() forgets it)
+    const bool ok = out_.set_format(fmt, pitch, initialized_ ? width_ : 0, initialized_ ? height_ : 0);
+    return ok ? EVX_SUCCESS : EVX_ERROR_INVALIDARG;
   }
   // decode()'s output as a device tensor written through desc (between frames
   // too; nullptr: back to the pixel formats).  Its strides are checked against
   // the frame size at each decode().
   evx_status set_output_tensor(const cairo_tensor *desc) {
-    if (desc && cairo_tensor_check(desc, nullptr, 1, 1, nullptr)) return EVX_ERROR_INVALIDARG;
-    tensor_ = desc != nullptr;
-    if (desc) tens_ = *desc;
-    return EVX_SUCCESS;
+    return out_.set_tensor(desc) ? EVX_SUCCESS : EVX_ERROR_INVALIDARG;
   }
   // The colour description decode() writes I420 / NV12 frames in (between
   // frames too; RGB frames ignore it).
   evx_status set_output_color(int range, int matrix) {
-    int32_t k[9], oy;
-    if (cairo_color_coefs(1, range, matrix, k, &oy)) return EVX_ERROR_INVALIDARG;
-    if (initialized_ && cairo_ctx_set_output_color(ctx_, range, matrix)) return EVX_ERROR_INVALIDARG;
-    range_ = range;
-    matrix_ = matrix;
-    return EVX_SUCCESS;
+    const bool ok = out_.set_color(1, range, matrix, initialized_ ? ctx_ : nullptr);
+    return ok ? EVX_SUCCESS : EVX_ERROR_INVALIDARG;
   }
 
  private:
@@ -123,7 +110,7 @@ class gpu_decoder : public evx1_decoder {
     wmb_ = wa_ / 16;
     hmb_ = ha_ / 16;
     if (cairo_ctx_create_ex(width_, height_, ring_, device_, 2, &ctx_)) return EVX_ERROR_HARDWAREFAIL;  // synchronous: 2 slots
-    (void)cairo_ctx_set_output_color(ctx_, range_, matrix_);  // (checked by set_output_color)
+    (void)cairo_ctx_set_output_color(ctx_, out_.range, out_.matrix);  // (checked by set_output_color)
     table_ = (cairo::BlockDesc *)calloc((size_t)wmb_ * hmb_, sizeof(cairo::BlockDesc));
     coef_ = (int16 *)calloc((size_t)wa_ * ha_ * 3 / 2, sizeof(int16));
     if (!table_ || !coef_) {
@@ -144,11 +131,7 @@ class gpu_decoder : public evx1_decoder {
   uint32 frame_index_;
   uint32 width_ = 0, height_ = 0, wa_ = 0, ha_ = 0, wmb_ = 0, hmb_ = 0, ring_ = 0;
   int device_ = 0;
-  int fmt_ = CAIRO_FMT_RGB24;  // output layout (set_output_format)
-  uint32 pitch_ = 0;
-  bool tensor_ = false;  // set_output_tensor: output is a device tensor written through tens_
-  cairo_tensor tens_{};
-  int range_ = CAIRO_RANGE_FULL, matrix_ = CAIRO_MATRIX_BT601;  // set_output_color
+  cairo::FrameIo out_;  // decode()'s output (set_output_format / _tensor / _color)
   cairo_ctx *ctx_ = nullptr;
   cairo::BlockDesc *table_ = nullptr;
   int16 *coef_ = nullptr;

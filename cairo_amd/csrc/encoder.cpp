@@ -16,6 +16,7 @@
 #include "../../include/evx1.h"
 #include "entropy.h"
 #include "evx_defs.h"
+#include "frame_io.h"
 #include "stream_format.h"
 
 namespace evx {
@@ -80,22 +81,13 @@ class gpu_encoder : public evx1_encoder {
       if (evx_failed(output->write_bytes(&h, sizeof(h)))) return EVX_ERROR_EXECUTION_FAILURE;
     }
     if (width != width_ || height != height_) return EVX_ERROR_INVALID_RESOURCE;
-    if (tensor_) {
-      if (cairo_tensor_check(&tens_, image, width, height, nullptr)) return EVX_ERROR_INVALIDARG;
-    } else if (cairo_frame_layout(fmt_, width, height, pitch_, nullptr, nullptr)) {
-      return EVX_ERROR_INVALIDARG;
-    }
+    if (in_.check(image, width, height)) return EVX_ERROR_INVALIDARG;
     frame_t f = frame_;
     if (evx_failed(output->write_bytes(&f, sizeof(f)))) return EVX_ERROR_EXECUTION_FAILURE;
 
     const auto t0 = std::chrono::steady_clock::now();
     int ticket = -1;
-    int r = tensor_ ? cairo_ctx_submit_tensor(ctx_, image, &tens_, frame_.index, frame_.type, frame_.quality, &ticket)
-            : fmt_ == CAIRO_FMT_RGB24 && !pitch_
-                ? cairo_ctx_submit(ctx_, (const uint8_t *)image, 0, frame_.index, frame_.type, frame_.quality,
-                                   &ticket)
-                : cairo_ctx_submit_fmt(ctx_, (const uint8_t *)image, 0, fmt_, pitch_, frame_.index, frame_.type,
-                                       frame_.quality, &ticket);
+    int r = cairo::submit_frame(ctx_, in_.source(image), frame_.index, frame_.type, frame_.quality, &ticket);
     if (r) return EVX_ERROR_EXECUTION_FAILURE;
     cairo_frame_result res;
     r = cairo_ctx_wait(ctx_, ticket, &res);
@@ -203,31 +195,21 @@ class gpu_encoder : public evx1_encoder {
   }
   // The layout encode() reads its image in (between frames too).
   evx_status set_input_format(int fmt, uint32 pitch) {
-    // before the first encode the frame size is not known: any even size stands in
-    const uint32 w = initialized_ ? width_ : 2, h = initialized_ ? height_ : 2;
-    if (cairo_frame_layout(fmt, w, h, initialized_ ? pitch : 0, nullptr, nullptr)) return EVX_ERROR_INVALIDARG;
-    fmt_ = fmt;
-    pitch_ = pitch;
-    return EVX_SUCCESS;
+    // (the frame size is known once initialised; clear() forgets it)
+    const bool ok = in_.set_format(fmt, pitch, initialized_ ? width_ : 0, initialized_ ? height_ : 0);
+    return ok ? EVX_SUCCESS : EVX_ERROR_INVALIDARG;
   }
   // encode()'s image as a device tensor read through desc (between frames too;
   // nullptr: back to the pixel formats).  Its strides are checked against the
   // frame size at each encode().
   evx_status set_input_tensor(const cairo_tensor *desc) {
-    if (desc && cairo_tensor_check(desc, nullptr, 1, 1, nullptr)) return EVX_ERROR_INVALIDARG;
-    tensor_ = desc != nullptr;
-    if (desc) tens_ = *desc;
-    return EVX_SUCCESS;
+    return in_.set_tensor(desc) ? EVX_SUCCESS : EVX_ERROR_INVALIDARG;
   }
   // The colour description of the I420 / NV12 images encode() reads (between
   // frames too; RGB images ignore it).
   evx_status set_input_color(int range, int matrix) {
-    int32_t k[9], oy;
-    if (cairo_color_coefs(0, range, matrix, k, &oy)) return EVX_ERROR_INVALIDARG;
-    if (initialized_ && cairo_ctx_set_input_color(ctx_, range, matrix)) return EVX_ERROR_INVALIDARG;
-    range_ = range;
-    matrix_ = matrix;
-    return EVX_SUCCESS;
+    const bool ok = in_.set_color(0, range, matrix, initialized_ ? ctx_ : nullptr);
+    return ok ? EVX_SUCCESS : EVX_ERROR_INVALIDARG;
   }
   // CAIRO_METRIC_* for the frames coded from now on (between frames too; the
   // synchronous encode() leaves no frame in flight), and the last frame's.
@@ -260,7 +242,7 @@ class gpu_encoder : public evx1_encoder {
     // the GPU precodes the entropy feed; only the arithmetic coder runs here
     if (cairo_ctx_set_outputs(ctx_, CAIRO_OUT_FEED)) return EVX_ERROR_HARDWAREFAIL;
     if (metrics_ && cairo_ctx_set_metrics(ctx_, metrics_)) return EVX_ERROR_HARDWAREFAIL;
-    if (cairo_ctx_set_input_color(ctx_, range_, matrix_)) return EVX_ERROR_HARDWAREFAIL;
+    if (cairo_ctx_set_input_color(ctx_, in_.range, in_.matrix)) return EVX_ERROR_HARDWAREFAIL;
     const size_t mbs = (size_t)((width + 15) / 16) * ((height + 15) / 16);
     last_table_ = (uint8 *)calloc(mbs, 16);
     if (!last_table_) return EVX_ERROR_OUTOFMEMORY;
@@ -276,11 +258,7 @@ class gpu_encoder : public evx1_encoder {
   uint32 width_ = 0, height_ = 0;
   uint32 ring_ = kDefaultRing;
   int device_ = 0;
-  int fmt_ = CAIRO_FMT_RGB24;  // input layout (set_input_format)
-  uint32 pitch_ = 0;
-  bool tensor_ = false;  // set_input_tensor: image is a device tensor read through tens_
-  cairo_tensor tens_{};
-  int range_ = CAIRO_RANGE_FULL, matrix_ = CAIRO_MATRIX_BT601;  // set_input_color
+  cairo::FrameIo in_;  // encode()'s image (set_input_format / _tensor / _color)
   cairo_ctx *ctx_ = nullptr;
   uint8 *last_table_ = nullptr;
   int metrics_ = 0;  // set_metrics

@@ -238,13 +238,11 @@ int cairo_stream_create(cairo_ctx* ctx, int threads, cairo_stream** out) {
   return kSuccess;
 }
 
-// cairo_stream_submit (fmt < 0: cairo_ctx_submit), cairo_stream_submit_fmt and,
-// with a source description, cairo_stream_submit_scaled; with a tensor
-// description, cairo_stream_submit_tensor.
-static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, int fmt, uint32_t pitch,
-                         const cairo_source* src, uint32_t index, uint32_t type, uint32_t quality, int* ticket,
-                         const cairo_tensor* tens = nullptr) {
-  if (!s || !rgb || !ticket) return kInvalidArg;
+// Every cairo_stream_submit* call: the frame as its cairo_ctx_submit* twin
+// describes it.
+static int stream_submit(cairo_stream* s, const cairo::FrameSource& src, uint32_t index, uint32_t type,
+                         uint32_t quality, int* ticket) {
+  if (!s || !src.base || !ticket) return kInvalidArg;
   const int t = s->next;
   {
     std::unique_lock<std::mutex> lk(s->m);
@@ -258,10 +256,7 @@ static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device,
     });
   }
   int tk = -1;
-  const int r = tens      ? cairo_ctx_submit_tensor(s->ctx, rgb, tens, index, type, quality, &tk)
-                : src     ? cairo_ctx_submit_scaled(s->ctx, rgb, fmt, pitch, src, index, type, quality, &tk)
-                : fmt < 0 ? cairo_ctx_submit(s->ctx, rgb, rgb_on_device, index, type, quality, &tk)
-                          : cairo_ctx_submit_fmt(s->ctx, rgb, rgb_on_device, fmt, pitch, index, type, quality, &tk);
+  const int r = cairo::submit_frame(s->ctx, src, index, type, quality, &tk);
   if (r) return r;
   {
     std::lock_guard<std::mutex> lk(s->m);
@@ -282,25 +277,27 @@ static int stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device,
 
 int cairo_stream_submit(cairo_stream* s, const uint8_t* rgb, int rgb_on_device, uint32_t index,
                         uint32_t type, uint32_t quality, int* ticket) {
-  return stream_submit(s, rgb, rgb_on_device, -1, 0, nullptr, index, type, quality, ticket);
+  return stream_submit(s, {rgb, rgb_on_device, CAIRO_FMT_RGB24, 0, false, nullptr, nullptr}, index, type, quality,
+                       ticket);
 }
 
 int cairo_stream_submit_fmt(cairo_stream* s, const uint8_t* frame, int on_device, int fmt, uint32_t pitch,
                             uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (fmt < 0) return kInvalidArg;
-  return stream_submit(s, frame, on_device, fmt, pitch, nullptr, index, type, quality, ticket);
+  return stream_submit(s, {frame, on_device, fmt, pitch, true, nullptr, nullptr}, index, type, quality, ticket);
 }
 
 int cairo_stream_submit_scaled(cairo_stream* s, const uint8_t* frame, int fmt, uint32_t pitch, const cairo_source* src,
                                uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
   if (fmt < 0 || !src) return kInvalidArg;
-  return stream_submit(s, frame, 1, fmt, pitch, src, index, type, quality, ticket);
+  return stream_submit(s, {frame, 1, fmt, pitch, true, src, nullptr}, index, type, quality, ticket);
 }
 
 int cairo_stream_submit_tensor(cairo_stream* s, const void* base, const cairo_tensor* desc, uint32_t index,
                                uint32_t type, uint32_t quality, int* ticket) {
   if (!desc) return kInvalidArg;
-  return stream_submit(s, (const uint8_t*)base, 1, -1, 0, nullptr, index, type, quality, ticket, desc);
+  return stream_submit(s, {(const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, nullptr, desc}, index, type, quality,
+                       ticket);
 }
 
 int cairo_stream_collect(cairo_stream* s, int ticket, uint8_t* out, uint64_t out_bytes,

@@ -28,10 +28,11 @@ struct ScaleFrame {
 };
 
 // Every scaled frame of one launch (grid.z = frame); all have the output size
-// dw x dh, the context's.
+// dw x dh, the context's.  A launch with more frames takes several kernels.
+constexpr int kScaleFrames = 48;
 struct ScaleArgs {
   int dw, dh, nframes, reserved;
-  ScaleFrame f[kMaxBatch];
+  ScaleFrame f[kScaleFrames];
 };
 static_assert(sizeof(ScaleArgs) <= 4096, "passed as kernel arguments");
 

@@ -232,7 +232,7 @@ int scale_plan(int fmt, uint32_t pitch, const cairo_source* src, uint32_t dw, ui
 }
 
 hipError_t launch_scale_batch(const ScaleArgs& a, hipStream_t s) {
-  if (a.nframes < 1 || a.nframes > kMaxBatch || a.dw < 2 || a.dh < 2 || 2 * a.dh > 65535) return hipErrorInvalidValue;
+  if (a.nframes < 1 || a.nframes > kScaleFrames || a.dw < 2 || a.dh < 2 || 2 * a.dh > 65535) return hipErrorInvalidValue;
   const int strips = (3 * a.dw + 3) / 4;  // of the widest plane row (RGB)
   hipLaunchKernelGGL(k_scale_batch, dim3((strips + kScaleThreads - 1) / kScaleThreads, 2 * a.dh, a.nframes),
                      dim3(kScaleThreads), 0, s, a);
