@@ -50,6 +50,9 @@ EVX_ERROR_INVALID_ARGS = 1
 # Pixel formats (include/cairo_amd.h CAIRO_FMT_*): a frame is one contiguous
 # uint8 buffer with a row pitch in bytes (0: tight); see frame_layout.
 FMT_RGB24, FMT_BGR24, FMT_I420, FMT_NV12 = range(4)
+# Capture and 10-bit layouts (packed 4:2:2, 16-bit words with the sample in the
+# high ten bits): taken as the NV12 frame they fold to, see frame_fold.
+FMT_YUY2, FMT_UYVY, FMT_P010 = 8, 9, 10
 # Colour description of an I420 / NV12 frame (include/cairo_amd.h CAIRO_RANGE_*,
 # CAIRO_MATRIX_*): (RANGE_FULL, MATRIX_BT601) is the codec's own space.
 RANGE_FULL, RANGE_LIMITED = 0, 1
@@ -97,6 +100,7 @@ def lib() -> ctypes.CDLL:
         "cairo_ctx_submit_fmt": (I, [P, P, I, I, U, U, U, U, ctypes.POINTER(I)]),
         "cairo_ctx_decode_frame_fmt": (I, [P, P, P, U, I, U, P]),
         "cairo_frame_layout": (I, [I, U, U, U, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(U)]),
+        "cairo_frame_fold": (I, [I, I, U, U, U, P, U, P]),
         "cairo_kat_convert": (I, [I, I, U, U, U, P, P, P, P, I]),
         "cairo_kat_convert_color": (I, [I, I, I, I, U, U, U, P, P, P, P, I]),
         "cairo_color_coefs": (I, [I, I, I, P, ctypes.POINTER(ctypes.c_int32)]),
@@ -237,13 +241,37 @@ def frame_layout(fmt: int, w: int, h: int, pitch: int = 0):
     """-> (bytes of a w x h frame of format fmt with row pitch `pitch`, its
     tight pitch); pitch 0 means tight (cairo_frame_layout).  ValueError for an
     unknown format, an odd or zero size, a pitch below the tight one, or an
-    odd I420 pitch.  No device needed."""
+    odd I420 or P010 pitch.  No device needed."""
     nb, tight = ctypes.c_uint64(), ctypes.c_uint32()
     ok = all(isinstance(x, (int, np.integer)) and 0 <= x < 2 ** 32 for x in (w, h, pitch)) and \
         isinstance(fmt, (int, np.integer)) and -2 ** 31 <= fmt < 2 ** 31
     if not ok or lib().cairo_frame_layout(int(fmt), int(w), int(h), int(pitch), ctypes.byref(nb), ctypes.byref(tight)):
         raise ValueError(f"no frame layout for format {fmt}, {w}x{h}, pitch {pitch}")
     return nb.value, tight.value
+
+
+def frame_fold(direction: int, fmt: int, frame: np.ndarray, w: int, h: int, pitch: int = 0,
+               nv12_pitch: int = 0) -> np.ndarray:
+    """The maps between a YUY2, UYVY or P010 frame and the NV12 frame the codec
+    takes in its place (cairo_frame_fold), on flat uint8 buffers of
+    frame_layout bytes.  direction 0 (fold): frame is of format fmt with row
+    pitch `pitch`; -> the NV12 frame with row pitch nv12_pitch.  direction 1
+    (unfold): frame is NV12 with row pitch nv12_pitch; -> the frame of format
+    fmt.  Pitch padding of the result is 0.  No device needed."""
+    if fmt not in (FMT_YUY2, FMT_UYVY, FMT_P010) or direction not in (0, 1):
+        raise ValueError(f"frame_fold is defined for FMT_YUY2, FMT_UYVY and FMT_P010, direction 0 or 1; got "
+                         f"format {fmt}, direction {direction}")
+    fb, _ = frame_layout(fmt, w, h, pitch)
+    nb, _ = frame_layout(FMT_NV12, w, h, nv12_pitch)
+    want = nb if direction else fb
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.nbytes != want or \
+            not frame.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"frame must be a C-contiguous uint8 array of {want} bytes")
+    out = np.zeros(fb if direction else nb, np.uint8)
+    f, n = (out, frame) if direction else (frame, out)
+    _ck(lib().cairo_frame_fold(int(direction), int(fmt), int(w), int(h), int(pitch), f.ctypes.data, int(nv12_pitch),
+                               n.ctypes.data), "cairo_frame_fold")
+    return out
 
 
 def color_coefs(direction: int, range: int, matrix: int):
@@ -260,8 +288,10 @@ def color_coefs(direction: int, range: int, matrix: int):
 
 def split_frame(buf: np.ndarray, fmt: int, w: int, h: int, pitch: int = 0):
     """Plane views of a frame buffer: (y, u, v) for I420, (y, uv) for NV12
-    (uv: (h/2, w/2, 2)), the (h, w, 3) pixels for the RGB formats; each view
-    covers the image only, not the pitch padding."""
+    (uv: (h/2, w/2, 2)), the (h, w, 3) pixels for the RGB formats; (y, u, v)
+    for YUY2 and UYVY (y: (h, w); u, v: (h, w/2), one sample per pixel pair and
+    row); (y, uv) as uint16 words for P010.  Each view covers the image only,
+    not the pitch padding."""
     nb, tight = frame_layout(fmt, w, h, pitch)
     p = pitch or tight
     b = np.asarray(buf).reshape(-1)
@@ -270,6 +300,15 @@ def split_frame(buf: np.ndarray, fmt: int, w: int, h: int, pitch: int = 0):
     if fmt in (FMT_RGB24, FMT_BGR24):
         return b.reshape(h, p)[:, :3 * w].reshape(h, w, 3) if p == tight else \
             np.lib.stride_tricks.as_strided(b, (h, w, 3), (p, 3, 1))
+    if fmt in (FMT_YUY2, FMT_UYVY):
+        o = 1 if fmt == FMT_UYVY else 0  # YUY2: Y0 U Y1 V; UYVY: U Y0 V Y1
+        at = lambda first, step, count: np.lib.stride_tricks.as_strided(b[first:], (h, count), (p, step))
+        return at(o, 2, w), at(1 - o, 4, w // 2), at(3 - o, 4, w // 2)
+    if fmt == FMT_P010:
+        words = b.view(np.uint16)  # (the pitch is even)
+        y = words[:p // 2 * h].reshape(h, p // 2)[:, :w]
+        uv = words[p // 2 * h:].reshape(h // 2, p // 2)[:, :w].reshape(h // 2, w // 2, 2)
+        return y, uv
     y = b[:p * h].reshape(h, p)[:, :w]
     if fmt == FMT_I420:
         cp, ch = p // 2, h // 2
@@ -795,13 +834,15 @@ class Context:
 
     def set_input_color(self, range: int, matrix: int) -> None:
         """The colour description (RANGE_*, MATRIX_*) of the I420 / NV12 frames
-        submitted from now on, also through a Stream; recorded per frame at
-        submit.  RGB frames ignore it.  Survives reset()."""
+        (and of the NV12 frame a YUY2 / UYVY / P010 frame folds to) submitted
+        from now on, also through a Stream; recorded per frame at submit.  RGB
+        frames ignore it.  Survives reset()."""
         _ck(self.L.cairo_ctx_set_input_color(self.h, range, matrix), "cairo_ctx_set_input_color")
 
     def set_output_color(self, range: int, matrix: int) -> None:
         """The colour description fetch_recon and cairo_ctx_decode_frame_fmt
-        write I420 / NV12 frames in from now on."""
+        write I420 / NV12 frames in from now on (YUY2 / UYVY / P010 frames are
+        the unfold of that NV12 frame)."""
         _ck(self.L.cairo_ctx_set_output_color(self.h, range, matrix), "cairo_ctx_set_output_color")
 
     def frame_metrics(self, ticket: int) -> dict:

@@ -582,8 +582,10 @@ int copy_frame(const cairo_ctx* c, uint8_t* staged, uint8_t* host, bool upload, 
                   : hipMemcpy2DAsync(host + hoff, hp, staged + soff, sp, row, rows, kind, st);
   };
   const size_t w = c->w, h = c->h;
-  CK(plane(0, tight, 0, pitch, tight, h));  // RGB rows, or the Y plane
-  if (fmt == CAIRO_FMT_I420) {
+  CK(plane(0, tight, 0, pitch, tight, h));  // RGB rows, packed 4:2:2 rows, or the Y plane
+  if (fmt == CAIRO_FMT_P010) {              // the UV rows: w 16-bit words each, like the Y rows
+    CK(plane((size_t)tight * h, tight, (size_t)pitch * h, pitch, tight, h / 2));
+  } else if (fmt == CAIRO_FMT_I420) {
     const size_t cw = w / 2, ch = h / 2, cp = pitch / 2;
     CK(plane(w * h, cw, (size_t)pitch * h, cp, cw, ch));
     CK(plane(w * h + cw * ch, cw, (size_t)pitch * h + cp * ch, cp, cw, ch));
@@ -2100,6 +2102,8 @@ int submit_frame(cairo_ctx* c, const FrameSource& src, uint32_t index, uint32_t 
       return kInvalidArg;
   } else if (cairo_frame_layout(src.fmt, c->w, c->h, src.pitch, &frame_bytes, &tight) != kSuccess) {
     return kInvalidArg;
+  } else if (kind == Pending::kDevice && src.fmt == CAIRO_FMT_P010 && ((uintptr_t)rgb & 1)) {
+    return kInvalidArg;  // 16-bit samples are read as such
   }
   std::lock_guard<std::mutex> lk(c->mu);
   CK(hipSetDevice(c->device));
@@ -2121,7 +2125,8 @@ int submit_frame(cairo_ctx* c, const FrameSource& src, uint32_t index, uint32_t 
   p.fmt = (uint8_t)src.fmt;
   p.pitch = kind == Pending::kDevice && src.pitch ? src.pitch : tight;  // whatever is staged is staged tight
   p.hpitch = src.pitch;
-  p.col = src.fmt == CAIRO_FMT_I420 || src.fmt == CAIRO_FMT_NV12 ? (uint8_t)c->in_col : 0;
+  // (the YUV formats: YUY2, UYVY and P010 are described as the NV12 frame they fold to)
+  p.col = src.fmt != CAIRO_FMT_RGB24 && src.fmt != CAIRO_FMT_BGR24 ? (uint8_t)c->in_col : 0;
   f.rgb = kind == Pending::kDevice ? rgb : slot_rgb(c, slot);
   if (kind == Pending::kScaled) {
     plan.dst = slot_rgb(c, slot);

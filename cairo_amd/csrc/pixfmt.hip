@@ -1,6 +1,6 @@
 // cairo_amd/csrc/pixfmt.hip -- pixel formats at the codec's edges: BGR24,
-// I420 and NV12 frames (and RGB24 with a row pitch) into the int16 4:2:0
-// source planes, and ring-slot planes out into any of the four formats.
+// I420, NV12, YUY2, UYVY and P010 frames (and RGB24 with a row pitch) into the
+// int16 4:2:0 source planes, and ring-slot planes out into any of the formats.
 //
 // The default launch (every frame tight RGB24) keeps k_convert_batch, and
 // cairo_ctx_decode_frame keeps k_yuv_to_rgb (kernels.hip): both are measured
@@ -14,8 +14,12 @@
 // right edge; nothing outside width x height is read or written on either
 // side, so the pitch padding of a destination keeps its bytes.
 //
-// I420 and NV12 frames carry a colour description (cairo_amd.h CAIRO_RANGE_*,
-// CAIRO_MATRIX_*).  Both strip functions take its mode as a
+// YUY2, UYVY and P010 frames are the NV12 frame they fold to
+// or unfold from (capfmt_pixel.h): 16 bytes of each row of a strip for the
+// packed 4:2:2 layouts, 16 of each Y row and 16 of the UV row for P010.
+//
+// The YUV frames carry a colour description (cairo_amd.h CAIRO_RANGE_*,
+// CAIRO_MATRIX_*; YUY2, UYVY and P010: of their NV12).  Both strip functions take its mode as a
 // template parameter, chosen once per workgroup like the format: identity (the
 // codec's own space: the code as it was), diagonal (LIMITED with BT601: no
 // chroma term in the luma) and full.
@@ -25,6 +29,7 @@
 #include <cstdio>
 
 #include "../../include/cairo_amd.h"
+#include "capfmt_pixel.h"
 #include "kernels.h"
 
 namespace cairo {
@@ -100,36 +105,68 @@ __device__ __forceinline__ int byte_of(const uint32_t (&w)[W], int k) {
   return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
 }
 
+// The unsigned integer of UNIT bytes: the narrow access of load_bytes and
+// store_bytes.
+template <int UNIT>
+struct Narrow {
+  typedef uint8_t type;
+};
+template <>
+struct Narrow<2> {
+  typedef uint16_t type;
+};
+
 // The first n of N bytes at p (N a multiple of 4) into dwords: dword loads
-// when all N are wanted and p is 4-byte aligned, else byte loads of the n
-// valid ones (the rest read as 0).
-template <int N>
+// when all N are wanted and p is 4-byte aligned, else loads of UNIT bytes of
+// the n valid ones (the rest read as 0).  UNIT 2: p is 2-byte aligned and n
+// even (16-bit samples).
+template <int N, int UNIT = 1>
 __device__ __forceinline__ void load_bytes(const uint8_t* p, int n, uint32_t (&w)[N / 4]) {
+  static_assert(UNIT == 1 || UNIT == 2, "byte or half-word accesses");
   if (n == N && ((uintptr_t)p & 3) == 0) {
     const uint32_t* q = (const uint32_t*)p;
 #pragma unroll
     for (int k = 0; k < N / 4; k++) w[k] = q[k];
   } else {
+    const typename Narrow<UNIT>::type* q = (const typename Narrow<UNIT>::type*)p;
 #pragma unroll
     for (int k = 0; k < N / 4; k++) w[k] = 0;
 #pragma unroll
-    for (int k = 0; k < N; k++)
-      if (k < n) w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3));
+    for (int k = 0; k < N; k += UNIT)
+      if (k < n) w[k >> 2] |= (uint32_t)q[k / UNIT] << (8 * (k & 3));
   }
 }
 
 // The first n of N bytes held in dwords to p; bytes from n on are not written.
-template <int N>
+template <int N, int UNIT = 1>
 __device__ __forceinline__ void store_bytes(uint8_t* p, int n, const uint32_t (&w)[N / 4]) {
+  static_assert(UNIT == 1 || UNIT == 2, "byte or half-word accesses");
   if (n == N && ((uintptr_t)p & 3) == 0) {
     uint32_t* q = (uint32_t*)p;
 #pragma unroll
     for (int k = 0; k < N / 4; k++) q[k] = w[k];
   } else {
+    typename Narrow<UNIT>::type* q = (typename Narrow<UNIT>::type*)p;
 #pragma unroll
-    for (int k = 0; k < N; k++)
-      if (k < n) p[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    for (int k = 0; k < N; k += UNIT)
+      if (k < n) q[k / UNIT] = (typename Narrow<UNIT>::type)(w[k >> 2] >> (8 * (k & 3)));
   }
+}
+
+// Half-word k of a little-endian dword array.
+template <int W>
+__device__ __forceinline__ uint32_t half_of(const uint32_t (&w)[W], int k) {
+  return (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+}
+
+static_assert(kFmtYuy2 == CAIRO_FMT_YUY2 && kFmtUyvy == CAIRO_FMT_UYVY && kFmtP010 == CAIRO_FMT_P010,
+              "capfmt_pixel.h names the header's values");
+
+// The formats whose samples are 8-bit YUV once read (for YUY2, UYVY and P010:
+// once folded), which a colour description applies to.
+constexpr bool fmt_is_yuv(int fmt) {
+  return fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_NV12 || fmt == CAIRO_FMT_YUY2 || fmt == CAIRO_FMT_UYVY ||
+         fmt == CAIRO_FMT_P010;
 }
 
 // The first n of N plane elements (N = 8: 16 bytes, N = 4: 8 bytes) at p as
@@ -177,12 +214,12 @@ __device__ __forceinline__ void load_i16(const int16_t* p, int n, int (&v)[N]) {
 // RGB24 / BGR24: the arithmetic of k_convert_batch (convert.cpp:11-14, 30-73).
 // I420 / NV12: the codec's own full-range BT.601 samples, Y + 16, U, V; under
 // a colour description, the same rule on the mapped samples.
+// YUY2 / UYVY / P010: the NV12 rule on the folded samples (capfmt_pixel.h).
 // ---------------------------------------------------------------------------
 template <int FMT, int MODE = kColorIdentity>
 __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pitch, const PlaneSet& in, int w, int h,
                                               int wa, int sx, int qy, const ColorMap& m) {
-  static_assert(MODE == kColorIdentity || FMT == CAIRO_FMT_I420 || FMT == CAIRO_FMT_NV12,
-                "a colour description applies to the YUV formats");
+  static_assert(MODE == kColorIdentity || fmt_is_yuv(FMT), "a colour description applies to the YUV formats");
   const int x0 = sx * kStrip;
   const int n = min(kStrip, w - x0);  // luma columns of this strip inside the image: 2, 4, 6 or 8
   const int nc = n >> 1;
@@ -205,27 +242,56 @@ __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pit
 #pragma unroll
     for (int k = 0; k < kStrip / 2; k++) uv[k] = (su[k] + 2) >> 2, vv[k] = (sv[k] + 2) >> 2;
   } else {
+    constexpr int ybase = MODE == kColorIdentity ? 16 : 0;
+    if constexpr (FMT == CAIRO_FMT_YUY2 || FMT == CAIRO_FMT_UYVY) {
+      uint32_t px[2][4];  // 16 bytes of each row: 4 pixel pairs
 #pragma unroll
-    for (int dy = 0; dy < 2; dy++) {
-      uint32_t py[2];
-      load_bytes<8>(frame + (size_t)(2 * qy + dy) * pitch + x0, n, py);
+      for (int dy = 0; dy < 2; dy++) {
+        load_bytes<16>(frame + (size_t)(2 * qy + dy) * pitch + 2 * x0, 2 * n, px[dy]);
 #pragma unroll
-      for (int k = 0; k < kStrip; k++) yv[dy][k] = byte_of(py, k) + (MODE == kColorIdentity ? 16 : 0);
-    }
-    const uint8_t* chroma = frame + (size_t)pitch * h;
-    if constexpr (FMT == CAIRO_FMT_I420) {
-      const size_t cp = pitch >> 1;
-      const uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
-      uint32_t pu[1], pv[1];
-      load_bytes<4>(up, nc, pu);
-      load_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
+        for (int k = 0; k < kStrip; k++) yv[dy][k] = byte_of(px[dy], cap_y_at(FMT, k)) + ybase;
+      }
 #pragma unroll
-      for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(pu, k), vv[k] = byte_of(pv, k);
+      for (int k = 0; k < kStrip / 2; k++) {
+        uv[k] = (int)cap_fold_chroma(byte_of(px[0], cap_u_at(FMT, k)), byte_of(px[1], cap_u_at(FMT, k)));
+        vv[k] = (int)cap_fold_chroma(byte_of(px[0], cap_v_at(FMT, k)), byte_of(px[1], cap_v_at(FMT, k)));
+      }
+    } else if constexpr (FMT == CAIRO_FMT_P010) {
+#pragma unroll
+      for (int dy = 0; dy < 2; dy++) {
+        uint32_t py[4];  // 8 words
+        load_bytes<16, 2>(frame + (size_t)(2 * qy + dy) * pitch + 2 * x0, 2 * n, py);
+#pragma unroll
+        for (int k = 0; k < kStrip; k++) yv[dy][k] = (int)cap_fold_p010(half_of(py, k)) + ybase;
+      }
+      uint32_t puv[4];  // 4 U, V word pairs
+      load_bytes<16, 2>(frame + (size_t)pitch * h + (size_t)qy * pitch + 2 * x0, 2 * n, puv);
+#pragma unroll
+      for (int k = 0; k < kStrip / 2; k++)
+        uv[k] = (int)cap_fold_p010(half_of(puv, 2 * k)), vv[k] = (int)cap_fold_p010(half_of(puv, 2 * k + 1));
     } else {
-      uint32_t puv[2];
-      load_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
 #pragma unroll
-      for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(puv, 2 * k), vv[k] = byte_of(puv, 2 * k + 1);
+      for (int dy = 0; dy < 2; dy++) {
+        uint32_t py[2];
+        load_bytes<8>(frame + (size_t)(2 * qy + dy) * pitch + x0, n, py);
+#pragma unroll
+        for (int k = 0; k < kStrip; k++) yv[dy][k] = byte_of(py, k) + ybase;
+      }
+      const uint8_t* chroma = frame + (size_t)pitch * h;
+      if constexpr (FMT == CAIRO_FMT_I420) {
+        const size_t cp = pitch >> 1;
+        const uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
+        uint32_t pu[1], pv[1];
+        load_bytes<4>(up, nc, pu);
+        load_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
+#pragma unroll
+        for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(pu, k), vv[k] = byte_of(pv, k);
+      } else {
+        uint32_t puv[2];
+        load_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
+#pragma unroll
+        for (int k = 0; k < kStrip / 2; k++) uv[k] = byte_of(puv, 2 * k), vv[k] = byte_of(puv, 2 * k + 1);
+      }
     }
     if constexpr (MODE != kColorIdentity) {
       color_strip<MODE, true>(m, yv, uv, vv);
@@ -240,6 +306,19 @@ __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pit
   const size_t co = (size_t)qy * (wa >> 1) + (x0 >> 1);
   store_i16<kStrip / 2>(in.u + co, nc, uv);
   store_i16<kStrip / 2>(in.v + co, nc, vv);
+}
+
+// The strip of a YUV format under colour description index col: the identity,
+// the diagonal map (LIMITED, BT601) or a full one.
+template <int FMT>
+__device__ __forceinline__ void convert_strip_col(int col, const uint8_t* frame, uint32_t pitch, const PlaneSet& in,
+                                                  int w, int h, int wa, int sx, int qy, const ColorMap& m) {
+  if (col == 0)
+    convert_strip<FMT>(frame, pitch, in, w, h, wa, sx, qy, m);
+  else if (col == 1)
+    convert_strip<FMT, kColorDiagonal>(frame, pitch, in, w, h, wa, sx, qy, m);
+  else
+    convert_strip<FMT, kColorFull>(frame, pitch, in, w, h, wa, sx, qy, m);
 }
 
 // Same grid convention as k_convert_batch: slice z < nframes converts frame z
@@ -262,22 +341,11 @@ __global__ __launch_bounds__(kFmtThreads) void k_convert_fmt_batch(ConvertFmtArg
   switch (e.fmt[blockIdx.z]) {  // uniform over the workgroup, as is col
     case CAIRO_FMT_RGB24: convert_strip<CAIRO_FMT_RGB24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
     case CAIRO_FMT_BGR24: convert_strip<CAIRO_FMT_BGR24>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
-    case CAIRO_FMT_I420:
-      if (col == 0)
-        convert_strip<CAIRO_FMT_I420>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
-      else if (col == 1)
-        convert_strip<CAIRO_FMT_I420, kColorDiagonal>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
-      else
-        convert_strip<CAIRO_FMT_I420, kColorFull>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
-      break;
-    default:
-      if (col == 0)
-        convert_strip<CAIRO_FMT_NV12>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
-      else if (col == 1)
-        convert_strip<CAIRO_FMT_NV12, kColorDiagonal>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
-      else
-        convert_strip<CAIRO_FMT_NV12, kColorFull>(frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m);
-      break;
+    case CAIRO_FMT_I420: convert_strip_col<CAIRO_FMT_I420>(col, frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
+    case CAIRO_FMT_YUY2: convert_strip_col<CAIRO_FMT_YUY2>(col, frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
+    case CAIRO_FMT_UYVY: convert_strip_col<CAIRO_FMT_UYVY>(col, frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
+    case CAIRO_FMT_P010: convert_strip_col<CAIRO_FMT_P010>(col, frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
+    default: convert_strip_col<CAIRO_FMT_NV12>(col, frame, pitch, in, e.c.w, e.c.h, e.c.wa, sx, qy, m); break;
   }
 }
 
@@ -286,12 +354,12 @@ __global__ __launch_bounds__(kFmtThreads) void k_convert_fmt_batch(ConvertFmtArg
 // RGB24 / BGR24: the arithmetic of k_yuv_to_rgb (convert.cpp:16-19, 162-223).
 // I420 / NV12: clamp(Y - 16), clamp(U), clamp(V) of the int16 samples; under a
 // colour description those 8-bit samples are then mapped.
+// YUY2 / UYVY / P010: the unfold of those NV12 samples (capfmt_pixel.h).
 // ---------------------------------------------------------------------------
 template <int FMT, int MODE = kColorIdentity>
 __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w, int h, uint32_t pitch, uint8_t* dst,
                                              int sx, int qy, const ColorMap& m) {
-  static_assert(MODE == kColorIdentity || FMT == CAIRO_FMT_I420 || FMT == CAIRO_FMT_NV12,
-                "a colour description applies to the YUV formats");
+  static_assert(MODE == kColorIdentity || fmt_is_yuv(FMT), "a colour description applies to the YUV formats");
   const int x0 = sx * kStrip;
   const int n = min(kStrip, w - x0);
   const int nc = n >> 1;
@@ -332,34 +400,74 @@ __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w,
     auto yb = [&](int dy, int k) { return MODE == kColorIdentity ? clamp8(yv[dy][k] - 16) : (uint32_t)yv[dy][k]; };
     auto ub = [&](int k) { return MODE == kColorIdentity ? clamp8(uv[k]) : (uint32_t)uv[k]; };
     auto vb = [&](int k) { return MODE == kColorIdentity ? clamp8(vv[k]) : (uint32_t)vv[k]; };
+    if constexpr (FMT == CAIRO_FMT_YUY2 || FMT == CAIRO_FMT_UYVY) {
+      uint32_t cu[kStrip / 2], cv[kStrip / 2];  // both rows of the pair carry the same chroma bytes
 #pragma unroll
-    for (int dy = 0; dy < 2; dy++) {
-      uint32_t py[2] = {};
+      for (int k = 0; k < kStrip / 2; k++) cu[k] = cap_pin(ub(k)), cv[k] = cap_pin(vb(k));
 #pragma unroll
-      for (int k = 0; k < kStrip; k++) py[k >> 2] |= yb(dy, k) << (8 * (k & 3));
-      store_bytes<8>(dst + (size_t)(2 * qy + dy) * pitch + x0, n, py);
-    }
-    uint8_t* chroma = dst + (size_t)pitch * h;
-    if constexpr (FMT == CAIRO_FMT_I420) {
-      const size_t cp = pitch >> 1;
-      uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
-      uint32_t pu[1] = {}, pv[1] = {};
+      for (int dy = 0; dy < 2; dy++) {
+        uint32_t px[4] = {};  // 4 pixel pairs
 #pragma unroll
-      for (int k = 0; k < kStrip / 2; k++) pu[0] |= ub(k) << (8 * k), pv[0] |= vb(k) << (8 * k);
-      store_bytes<4>(up, nc, pu);
-      store_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
-    } else {
-      uint32_t puv[2] = {};
+        for (int k = 0; k < kStrip; k++) px[k >> 1] |= cap_pin(yb(dy, k)) << (8 * (cap_y_at(FMT, k) & 3));
+#pragma unroll
+        for (int k = 0; k < kStrip / 2; k++)
+          px[k] |= (cu[k] << (8 * (cap_u_at(FMT, k) & 3))) | (cv[k] << (8 * (cap_v_at(FMT, k) & 3)));
+        store_bytes<16>(dst + (size_t)(2 * qy + dy) * pitch + 2 * x0, 2 * n, px);
+      }
+    } else if constexpr (FMT == CAIRO_FMT_P010) {
+#pragma unroll
+      for (int dy = 0; dy < 2; dy++) {
+        uint32_t py[4] = {};  // 8 words
+#pragma unroll
+        for (int k = 0; k < kStrip; k++) py[k >> 1] |= cap_unfold_p010(cap_pin(yb(dy, k))) << (16 * (k & 1));
+        store_bytes<16, 2>(dst + (size_t)(2 * qy + dy) * pitch + 2 * x0, 2 * n, py);
+      }
+      uint32_t puv[4] = {};  // 4 U, V word pairs
 #pragma unroll
       for (int k = 0; k < kStrip / 2; k++)
-        puv[k >> 1] |= (ub(k) | (vb(k) << 8)) << (16 * (k & 1));
-      store_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
+        puv[k] = cap_unfold_p010(cap_pin(ub(k))) | (cap_unfold_p010(cap_pin(vb(k))) << 16);
+      store_bytes<16, 2>(dst + (size_t)pitch * h + (size_t)qy * pitch + 2 * x0, 2 * n, puv);
+    } else {
+#pragma unroll
+      for (int dy = 0; dy < 2; dy++) {
+        uint32_t py[2] = {};
+#pragma unroll
+        for (int k = 0; k < kStrip; k++) py[k >> 2] |= yb(dy, k) << (8 * (k & 3));
+        store_bytes<8>(dst + (size_t)(2 * qy + dy) * pitch + x0, n, py);
+      }
+      uint8_t* chroma = dst + (size_t)pitch * h;
+      if constexpr (FMT == CAIRO_FMT_I420) {
+        const size_t cp = pitch >> 1;
+        uint8_t* up = chroma + (size_t)qy * cp + (x0 >> 1);
+        uint32_t pu[1] = {}, pv[1] = {};
+#pragma unroll
+        for (int k = 0; k < kStrip / 2; k++) pu[0] |= ub(k) << (8 * k), pv[0] |= vb(k) << (8 * k);
+        store_bytes<4>(up, nc, pu);
+        store_bytes<4>(up + cp * (size_t)(h >> 1), nc, pv);
+      } else {
+        uint32_t puv[2] = {};
+#pragma unroll
+        for (int k = 0; k < kStrip / 2; k++)
+          puv[k >> 1] |= (ub(k) | (vb(k) << 8)) << (16 * (k & 1));
+        store_bytes<8>(chroma + (size_t)qy * pitch + x0, n, puv);
+      }
     }
   }
 }
 
+template <int FMT>
+__device__ __forceinline__ void planes_strip_col(int col, const PlaneSet& src, int sp, int w, int h, uint32_t pitch,
+                                                 uint8_t* dst, int sx, int qy, const ColorMap& m) {
+  if (col == 0)
+    planes_strip<FMT>(src, sp, w, h, pitch, dst, sx, qy, m);
+  else if (col == 1)
+    planes_strip<FMT, kColorDiagonal>(src, sp, w, h, pitch, dst, sx, qy, m);
+  else
+    planes_strip<FMT, kColorFull>(src, sp, w, h, pitch, dst, sx, qy, m);
+}
+
 // col / m: the colour description index of the frame written and its output
-// map (used for I420 / NV12 only).
+// map (used for the YUV formats only).
 __global__ __launch_bounds__(kFmtThreads) void k_planes_to_fmt(PlaneSet src, int sp, int w, int h, int fmt,
                                                                uint32_t pitch, uint8_t* dst, int col, ColorMap m) {
   const int sx = blockIdx.x * kFmtThreads + threadIdx.x, qy = blockIdx.y;
@@ -367,22 +475,11 @@ __global__ __launch_bounds__(kFmtThreads) void k_planes_to_fmt(PlaneSet src, int
   switch (fmt) {
     case CAIRO_FMT_RGB24: planes_strip<CAIRO_FMT_RGB24>(src, sp, w, h, pitch, dst, sx, qy, m); break;
     case CAIRO_FMT_BGR24: planes_strip<CAIRO_FMT_BGR24>(src, sp, w, h, pitch, dst, sx, qy, m); break;
-    case CAIRO_FMT_I420:
-      if (col == 0)
-        planes_strip<CAIRO_FMT_I420>(src, sp, w, h, pitch, dst, sx, qy, m);
-      else if (col == 1)
-        planes_strip<CAIRO_FMT_I420, kColorDiagonal>(src, sp, w, h, pitch, dst, sx, qy, m);
-      else
-        planes_strip<CAIRO_FMT_I420, kColorFull>(src, sp, w, h, pitch, dst, sx, qy, m);
-      break;
-    default:
-      if (col == 0)
-        planes_strip<CAIRO_FMT_NV12>(src, sp, w, h, pitch, dst, sx, qy, m);
-      else if (col == 1)
-        planes_strip<CAIRO_FMT_NV12, kColorDiagonal>(src, sp, w, h, pitch, dst, sx, qy, m);
-      else
-        planes_strip<CAIRO_FMT_NV12, kColorFull>(src, sp, w, h, pitch, dst, sx, qy, m);
-      break;
+    case CAIRO_FMT_I420: planes_strip_col<CAIRO_FMT_I420>(col, src, sp, w, h, pitch, dst, sx, qy, m); break;
+    case CAIRO_FMT_YUY2: planes_strip_col<CAIRO_FMT_YUY2>(col, src, sp, w, h, pitch, dst, sx, qy, m); break;
+    case CAIRO_FMT_UYVY: planes_strip_col<CAIRO_FMT_UYVY>(col, src, sp, w, h, pitch, dst, sx, qy, m); break;
+    case CAIRO_FMT_P010: planes_strip_col<CAIRO_FMT_P010>(col, src, sp, w, h, pitch, dst, sx, qy, m); break;
+    default: planes_strip_col<CAIRO_FMT_NV12>(col, src, sp, w, h, pitch, dst, sx, qy, m); break;
   }
 }
 
@@ -443,15 +540,29 @@ extern "C" {
 
 int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint32_t pitch, uint64_t* bytes,
                        uint32_t* tight_pitch) {
-  if (fmt < CAIRO_FMT_RGB24 || fmt > CAIRO_FMT_NV12 || !width || !height || (width & 1) || (height & 1))
+  const bool cap = fmt >= CAIRO_FMT_YUY2 && fmt <= CAIRO_FMT_P010;  // (4..7 are unassigned)
+  if (fmt < CAIRO_FMT_RGB24 || (fmt > CAIRO_FMT_NV12 && !cap) || !width || !height || (width & 1) || (height & 1))
     return kInvalidArg;
   const bool rgb = fmt == CAIRO_FMT_RGB24 || fmt == CAIRO_FMT_BGR24;
-  const uint64_t tight = rgb ? (uint64_t)3 * width : width;
+  const bool one_plane = rgb || fmt == CAIRO_FMT_YUY2 || fmt == CAIRO_FMT_UYVY;
+  const uint64_t tight = rgb ? (uint64_t)3 * width : cap ? (uint64_t)2 * width : width;
   if (tight > 0xFFFFFFFFull) return kInvalidArg;
   const uint64_t p = pitch ? pitch : tight;
-  if (p < tight || (fmt == CAIRO_FMT_I420 && (p & 1))) return kInvalidArg;
-  if (bytes) *bytes = rgb ? p * height : p * height + p * (height / 2);  // 4:2:0: chroma rows hold pitch bytes in all
+  if (p < tight || ((fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_P010) && (p & 1))) return kInvalidArg;
+  // 4:2:0: chroma rows hold pitch bytes in all
+  if (bytes) *bytes = one_plane ? p * height : p * height + p * (height / 2);
   if (tight_pitch) *tight_pitch = (uint32_t)tight;
+  return kSuccess;
+}
+
+int cairo_frame_fold(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, uint8_t* frame, uint32_t nv12_pitch,
+                     uint8_t* nv12) {
+  uint32_t tight = 0, ntight = 0;
+  if (dir < 0 || dir > 1 || !frame || !nv12 || fmt < CAIRO_FMT_YUY2 || fmt > CAIRO_FMT_P010 ||
+      cairo_frame_layout(fmt, w, h, pitch, nullptr, &tight) != kSuccess ||
+      cairo_frame_layout(CAIRO_FMT_NV12, w, h, nv12_pitch, nullptr, &ntight) != kSuccess)
+    return kInvalidArg;
+  frame_fold_loops(dir, fmt, w, h, pitch ? pitch : tight, frame, nv12_pitch ? nv12_pitch : ntight, nv12);
   return kSuccess;
 }
 
@@ -477,8 +588,7 @@ int cairo_kat_convert_color(int dir, int fmt, int range, int matrix, uint32_t w,
   if (dir < 0 || dir > 1 || !frame || !y || !u || !v || w > (1u << 20) || h > 2 * 65535u || !color_known(range, matrix) ||
       cairo_frame_layout(fmt, w, h, pitch, &bytes, &tight) != kSuccess)
     return kInvalidArg;
-  const bool yuv = fmt == CAIRO_FMT_I420 || fmt == CAIRO_FMT_NV12;
-  const int col = yuv ? color_index(range, matrix) : 0;  // an RGB frame has no description
+  const int col = fmt_is_yuv(fmt) ? color_index(range, matrix) : 0;  // an RGB frame has no description
   if (!pitch) pitch = tight;
   int r = fail(hipSetDevice(device), "hipSetDevice");
   if (r) return r;

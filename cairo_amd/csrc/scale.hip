@@ -201,6 +201,9 @@ int scale_plan(int fmt, uint32_t pitch, const cairo_source* src, uint32_t dw, ui
                uint8_t* dst, ScaleFrame* out) {
   if (!src || src->reserved[0] || src->reserved[1]) return kInvalidArg;
   uint32_t tight = 0;
+  // The kernel walks planes of equally interleaved bytes: packed 4:2:2 (YUY2,
+  // UYVY) and 16-bit samples (P010) are not scaled.
+  if (fmt > CAIRO_FMT_NV12) return kInvalidArg;
   // format, even non-zero sizes, pitch against the source's width
   if (cairo_frame_layout(fmt, src->width, src->height, pitch, nullptr, &tight) != kSuccess ||
       cairo_frame_layout(fmt, dw, dh, 0, nullptr, nullptr) != kSuccess)

@@ -62,7 +62,12 @@ extern "C" {
  *      cairo_tensor_check, cairo_tensor_host, cairo_kat_tensor,
  *      cairo_ctx_submit_tensor, cairo_stream_submit_tensor,
  *      cairo_ctx_decode_frame_tensor, cairo_ctx_fetch_recon_tensor,
- *      evx_encoder_set_input_tensor, evx_decoder_set_output_tensor. */
+ *      evx_encoder_set_input_tensor, evx_decoder_set_output_tensor.
+ *   4  (unchanged) capture and 10-bit frames add values and one entry point
+ *      only: the enumerators CAIRO_FMT_YUY2, CAIRO_FMT_UYVY and CAIRO_FMT_P010
+ *      (8, 9, 10; values the entry points above refused before) and
+ *      cairo_frame_fold.  Every call that took a format value takes them,
+ *      except the scaled submit.  Nothing existing changes. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -86,12 +91,76 @@ typedef struct cairo_ctx cairo_ctx;
  * and written under a colour description (below).
  * Pixels outside width x height are never read; on output the bytes of a row
  * beyond the image (the pitch padding) are never written. */
+
+/* ---- capture and 10-bit frames ----------------------------
+ * Frame layouts added after ABI 4 was pinned; 4..7 stay unassigned and refused. */
+enum { CAIRO_FMT_YUY2 = 8, CAIRO_FMT_UYVY = 9, CAIRO_FMT_P010 = 10 };
+/* What capture cards (packed 4:2:2) and 10-bit hardware decoders (P010) leave
+ * in memory.  Widths and heights are even, as for every format.
+ *   YUY2  one plane: height rows of pitch bytes; per pixel pair the four bytes
+ *         Y0 U Y1 V.  Tight pitch 2*width, pitch*height bytes; pitch >= 2*width,
+ *         any byte alignment of base and pitch.
+ *   UYVY  the same with the bytes U Y0 V Y1.
+ *   P010  16-bit little-endian words.  Y: height rows of pitch bytes, width
+ *         words each; then height/2 rows of pitch bytes of interleaved U, V
+ *         words (U first), width words each.  Tight pitch 2*width,
+ *         pitch*height + pitch*(height/2) bytes; pitch even and >= 2*width.  A
+ *         device frame's base must be 2-byte aligned (else
+ *         EVX_ERROR_INVALID_ARGS).  The ten significant bits of a word are its
+ *         high ten, v10 = word >> 6; the low six bits are ignored on input and
+ *         written as zero on output.
+ * The codec keeps 8-bit 4:2:0.  Each layout is defined by two pure
+ * frame-to-frame maps onto NV12 of the same size, and everything else is what
+ * the NV12 frame gets.
+ *
+ * fold (dir 0): a frame of the layout -> the NV12 frame (Y8 plane; U8, V8 at
+ * (cx, cy), cx < width/2, cy < height/2).
+ *   YUY2 / UYVY: Y8(x, y) = Y(x, y).  With U(cx, y) the U byte of pixel pair cx
+ *     of row y:  U8(cx, cy) = (U(cx, 2cy) + U(cx, 2cy+1) + 1) >> 1, and V8
+ *     likewise from V.  A 4:2:0 chroma sample lies between the two rows whose
+ *     4:2:2 samples it replaces; the rule is their mean, halves rounded up (the
+ *     rounding of the scaled submit's exact 2:1).
+ *   P010: every sample, luma and chroma alike, is
+ *     s8 = min((v10 + 2) >> 2, 255): round to nearest, halves up, clamped.
+ *     Limited-range 10-bit code points land on their 8-bit ones (64 -> 16,
+ *     940 -> 235, 960 -> 240).
+ * unfold (dir 1): an NV12 frame -> the frame of the layout.
+ *   YUY2 / UYVY: Y(x, y) = Y8(x, y); rows 2cy and 2cy+1 both get U8(cx, cy)
+ *     and V8(cx, cy) for pair cx: the codec's rule that the luma sample at
+ *     (x, y) uses the chroma sample at (x>>1, y>>1).
+ *   P010: word = s8 << 8 for every sample.
+ * fold(unfold(f)) == f for every NV12 frame f, in all three layouts (the mean
+ * of two equal samples is that sample; ((s8 << 2) + 2) >> 2 == s8).
+ *
+ * Composition.  Input: submitting a frame of one of these layouts gives
+ * exactly the bits of submitting fold(frame) as NV12 under the same input
+ * colour description; the colour map runs on the folded 8-bit samples, and the
+ * source side of the per-frame metrics is what the folded frame carries.
+ * Output: cairo_ctx_decode_frame_fmt and cairo_ctx_fetch_recon write unfold of
+ * the NV12 frame they would write under the same output colour description
+ * (the colour map runs before the unfold).
+ *
+ * Refusals (EVX_ERROR_INVALID_ARGS).  cairo_scale_check,
+ * cairo_ctx_submit_scaled and cairo_stream_submit_scaled refuse the three
+ * layouts: the scale kernel walks planes of equally interleaved bytes, which
+ * neither packed 4:2:2 nor 16-bit samples are; the refused submit takes no
+ * ticket.  P010 with an odd pitch, or a P010 device frame at an odd address,
+ * is refused.  Format values 4..7 and above 10 are refused as before. */
+
 /* Buffer size and tight pitch of a frame (no device needed).
  * EVX_ERROR_INVALID_ARGS for an unknown format, an odd or zero size, a pitch
- * below the tight pitch, or an odd pitch for I420.  bytes / tight_pitch may be
- * NULL. */
+ * below the tight pitch, or an odd pitch for I420 or P010.  bytes /
+ * tight_pitch may be NULL. */
 CAIRO_API int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint32_t pitch,
                                  uint64_t *bytes, uint32_t *tight_pitch);
+/* fold and unfold on host buffers, with the per-sample code the kernels run
+ * (no device needed).  fmt is CAIRO_FMT_YUY2, _UYVY or _P010; frame has row
+ * pitch `pitch` and nv12 row pitch nv12_pitch (0: tight).  dir 0 reads frame
+ * and writes the NV12 image bytes, dir 1 reads nv12 and writes the frame's
+ * image bytes; pitch padding is never written.  EVX_ERROR_INVALID_ARGS for any
+ * other format or a layout that cairo_frame_layout refuses. */
+CAIRO_API int cairo_frame_fold(int dir, int fmt, uint32_t w, uint32_t h, uint32_t pitch, uint8_t *frame,
+                               uint32_t nv12_pitch, uint8_t *nv12);
 
 /* ---- colour descriptions ----------------------------------
  * A colour description is a pair (range, matrix): */
@@ -100,9 +169,10 @@ CAIRO_API int cairo_frame_layout(int fmt, uint32_t width, uint32_t height, uint3
 #define CAIRO_MATRIX_BT601  0   /* Kr = 0.299,  Kb = 0.114 (today) */
 #define CAIRO_MATRIX_BT709  1   /* Kr = 0.2126, Kb = 0.0722 */
 /* (FULL, BT601) is the codec's own space and the identity.  The description
- * applies only to the 8-bit samples of I420 and NV12 frames.  RGB24 and BGR24
- * frames are taken and returned exactly as today whatever the description is,
- * so one launch and one ladder may mix them.
+ * applies only to the 8-bit samples of I420 and NV12 frames (and of the NV12
+ * frame a YUY2, UYVY or P010 frame folds to or unfolds from, above).  RGB24
+ * and BGR24 frames are taken and returned exactly as today whatever the
+ * description is, so one launch and one ladder may mix them.
  *
  * Two maps are defined on the 8-bit sample triple:
  *   dir 0: described YUV to the codec's full-range BT.601 (input).

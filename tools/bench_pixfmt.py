@@ -10,6 +10,12 @@ tests/test_pixfmt.py), then RGB24 and NV12 once more from pinned host memory
 (the PCIe-inclusive rate).  After timing, each format's block tables of the
 first `--check-frames` frames are compared with the RGB24 run's.
 
+Capture and 10-bit layouts: YUY2, UYVY and P010 legs carry
+the unfold of the NV12 frames (cairo_frame_fold), whose fold is that NV12 frame
+again, so their tables are compared with the same run's; P010 runs from pinned
+host memory as well (as many bytes per frame as RGB24).  "capfmt" relates each
+resident leg to the NV12 legs of this process and their spread.
+
 Colour descriptions: the resident NV12 leg runs a second time
 ("nv12_repeat"), so that the identity leg's own run-to-run spread in this
 process is known, and then once more with the same bytes *interpreted* as
@@ -36,7 +42,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CONFIGS = {"4k": (3840, 2160, 4, 16), "1080p": (1920, 1080, 4, 8), "720p": (1280, 720, 2, 16), "cif": (352, 288, 4, 16)}
-NAMES = ("rgb24", "bgr24", "i420", "nv12")
+NAMES = {0: "rgb24", 1: "bgr24", 2: "i420", 3: "nv12", 8: "yuy2", 9: "uyvy", 10: "p010"}
+CAP_FMTS = (8, 9, 10)  # FMT_YUY2, FMT_UYVY, FMT_P010
 
 
 def yuv_frame(cairo_amd, rgb, fmt):
@@ -123,6 +130,10 @@ def main():
     p.add_argument("--check-frames", type=int, default=48)
     p.add_argument("--no-color", dest="color", action="store_false",
                    help="skip the NV12 repeat and the NV12 LIMITED / BT709 legs")
+    p.add_argument("--no-capfmt", dest="capfmt", action="store_false", help="skip the YUY2, UYVY and P010 legs")
+    p.add_argument("--formats", default=None, metavar="NAMES",
+                   help="comma-separated resident legs to run alone (for a kernel trace of one format): no host-fed "
+                        "legs, no table check, no comparisons")
     a = p.parse_args()
     import torch  # device and pinned memory only; before the library starts HIP
 
@@ -142,7 +153,13 @@ def main():
            "warmup_frames": warm, "timed_frames": timed, "pool_frames": pool_n, "unit": "Mpix/s", "resident": {},
            "host_fed": {}, "tables_equal_rgb24": {}}
     ref_tables = None
-    for fmt in range(4):
+    legs = (0, 1, 2, 3) + (CAP_FMTS if a.capfmt else ())
+    if a.formats:
+        legs = tuple(f for f in legs if NAMES[f] in a.formats.split(","))
+        a.check_frames, a.host_steps, a.color, a.capfmt = 0, 0, False, False
+    for fmt in legs:
+        if fmt in CAP_FMTS:  # built when its turn comes and dropped after it: a P010 pool is as large as the RGB one
+            host[fmt] = [cairo_amd.frame_fold(1, fmt, f, w, h) for f in host[3]]
         nb = host[fmt][0].nbytes
         dev = torch.empty((pool_n, nb), dtype=torch.uint8, device="cuda")
         for i, f in enumerate(host[fmt]):
@@ -155,7 +172,7 @@ def main():
         res["resident"][NAMES[fmt]] = out
         if fmt == 0:
             ref_tables = tables
-        else:
+        elif not a.formats:
             res["tables_equal_rgb24"][NAMES[fmt]] = len(tables) == len(ref_tables) and all(
                 np.array_equal(x, y) for x, y in zip(tables, ref_tables))
         if fmt == cairo_amd.FMT_NV12 and a.color:
@@ -178,10 +195,20 @@ def main():
                   flush=True)
         del dev
         torch.cuda.empty_cache()
+        if fmt in (8, 9):
+            del host[fmt]
         print(f"[bench_pixfmt] {NAMES[fmt]}: {out}", file=sys.stderr, flush=True)
+    if a.capfmt:
+        nv = [res["resident"][k]["value"] for k in ("nv12", "nv12_repeat") if k in res["resident"]]
+        lo, hi = min(nv), max(nv)
+        res["capfmt"] = {"nv12_runs": nv, "nv12_spread_pct": round(100 * (hi - lo) / lo, 3)}
+        for fmt in CAP_FMTS:
+            v = res["resident"][NAMES[fmt]]["value"]
+            res["capfmt"][NAMES[fmt]] = {"value": v, "vs_nv12_low_pct": round(100 * (v / lo - 1), 3),
+                                         "below_nv12_by_more_than_its_spread": v < lo - (hi - lo)}
     if a.host_steps:
         n = 2 * batch
-        for fmt in (0, 3):
+        for fmt in (0, 3) + ((10,) if a.capfmt else ()):
             nb = host[fmt][0].nbytes
             pinned = torch.empty((n, nb), dtype=torch.uint8, pin_memory=True)
             hv = pinned.numpy()
