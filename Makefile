@@ -68,6 +68,7 @@ check-knobs:
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_TOOLS_BUILD -DCAIRO_ATTR_SKIP=120 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/attr120.o
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_MAX_BATCH=64 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/batch64.o
 	$(HIPCC) $(HIPFLAGS) -DCAIRO_MAX_BATCH=64 -c $(SRC)/backend.hip -o $(KNOB_OBJ)/batch64_backend.o
+	$(HIPCC) $(HIPFLAGS) -DCAIRO_MAX_BATCH=64 -c $(SRC)/pixfmt.hip -o $(KNOB_OBJ)/batch64_pixfmt.o
 	@if $(HIPCC) $(HIPFLAGS) -DCAIRO_ATTR_SKIP=1 -c $(SRC)/kernels.hip -o $(KNOB_OBJ)/refused.o 2>/dev/null; then \
 	  echo "CAIRO_ATTR_SKIP without CAIRO_TOOLS_BUILD was not refused"; exit 1; fi
 	@echo "check-knobs: every build switch compiles; CAIRO_ATTR_SKIP is refused in product builds"

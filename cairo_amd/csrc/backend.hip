@@ -32,6 +32,7 @@
 
 #include "../../include/cairo_amd.h"
 #include "ctx_internal.h"
+#include "hip_status.h"
 #include "kernels.h"
 #include "metrics.h"
 #include "precode.h"
@@ -74,8 +75,6 @@ constexpr size_t kCoefChunkBytes = size_t(1) << 30;
 // frame m in slot (m % N) * S + (m / N) % S -- its producer's own block, a
 // mirror block on every other member -- for any N <= kMaxGroup.
 constexpr int kMirrorSlots = kMaxGroup > kMaxRing ? kMaxGroup : kMaxRing;
-constexpr int kSuccess = 0, kInvalidArg = 1, kOutOfMemory = 3, kHardwareFail = 5,  // evx_status (base.h:150-172)
-              kInvalidResource = 8;
 
 struct Stage {
   uint8_t* table = nullptr;  // pinned, mapped (k_feed_copy writes it in feed mode)
@@ -285,11 +284,6 @@ namespace {
 
 using Pending = cairo_ctx::Pending;
 
-int fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return kSuccess;
-  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
-  return kHardwareFail;
-}
 #define CK(x)                                   \
   do {                                          \
     int _r = fail((x), #x);                     \
@@ -1513,11 +1507,6 @@ int cairo_ctx_decode_frame_tensor(cairo_ctx* c, const uint8_t* table, const int1
   return decode_frame(c, table, coef, index, {(uint8_t*)base, kSinkRgb888, 0, desc});
 }
 
-static bool color_known(int range, int matrix) {
-  return (range == CAIRO_RANGE_FULL || range == CAIRO_RANGE_LIMITED) &&
-         (matrix == CAIRO_MATRIX_BT601 || matrix == CAIRO_MATRIX_BT709);
-}
-
 static int set_color(cairo_ctx* c, int cairo_ctx::*col, int range, int matrix) {
   if (!c || !color_known(range, matrix)) return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -2033,34 +2022,17 @@ int cairo_kat_transform(const int16_t* src, const int16_t* pred, const uint8_t* 
   if (!src || !pred || !qtype || !coef || !recon || !qvar || count <= 0) return kInvalidArg;
   CK(hipSetDevice(device));
   const size_t n = (size_t)count * 384;
-  int16_t *ds = nullptr, *dp = nullptr, *dc = nullptr, *dr = nullptr;
-  uint8_t* dq = nullptr;
-  int32_t* dv = nullptr;
-  int r = kSuccess;
-  if ((r = fail(hipMalloc(&ds, n * 2), "malloc")) || (r = fail(hipMalloc(&dp, n * 2), "malloc")) ||
-      (r = fail(hipMalloc(&dc, n * 2), "malloc")) || (r = fail(hipMalloc(&dr, n * 2), "malloc")) ||
-      (r = fail(hipMalloc(&dq, (size_t)count * 2), "malloc")) ||
-      (r = fail(hipMalloc(&dv, (size_t)count * 8), "malloc")))
-    goto done;
-  if ((r = fail(hipMemcpy(ds, src, n * 2, hipMemcpyHostToDevice), "h2d")) ||
-      (r = fail(hipMemcpy(dp, pred, n * 2, hipMemcpyHostToDevice), "h2d")) ||
-      (r = fail(hipMemcpy(dq, qtype, (size_t)count * 2, hipMemcpyHostToDevice), "h2d")))
-    goto done;
-  if ((r = fail(launch_kat_transform(ds, dp, dc, dr, dq, dv, count, nullptr), "kat")) ||
-      (r = fail(hipDeviceSynchronize(), "sync")))
-    goto done;
-  if ((r = fail(hipMemcpy(coef, dc, n * 2, hipMemcpyDeviceToHost), "d2h")) ||
-      (r = fail(hipMemcpy(recon, dr, n * 2, hipMemcpyDeviceToHost), "d2h")) ||
-      (r = fail(hipMemcpy(qvar, dv, (size_t)count * 8, hipMemcpyDeviceToHost), "d2h")))
-    goto done;
-done:
-  (void)hipFree(ds);
-  (void)hipFree(dp);
-  (void)hipFree(dc);
-  (void)hipFree(dr);
-  (void)hipFree(dq);
-  (void)hipFree(dv);
-  return r;
+  KatBuffer ds, dp, dc, dr, dq, dv;
+  int r;
+  if ((r = ds.alloc(n * 2)) || (r = dp.alloc(n * 2)) || (r = dc.alloc(n * 2)) || (r = dr.alloc(n * 2)) ||
+      (r = dq.alloc((size_t)count * 2)) || (r = dv.alloc((size_t)count * 8)) || (r = ds.upload(src, n * 2)) ||
+      (r = dp.upload(pred, n * 2)) || (r = dq.upload(qtype, (size_t)count * 2)) ||
+      (r = kat_run(launch_kat_transform(ds.as<int16_t>(), dp.as<int16_t>(), dc.as<int16_t>(), dr.as<int16_t>(),
+                                        dq.as<uint8_t>(), dv.as<int32_t>(), count, nullptr),
+                   "kat")) ||
+      (r = dc.download(coef, n * 2)) || (r = dr.download(recon, n * 2)) || (r = dv.download(qvar, (size_t)count * 8)))
+    return r;
+  return kSuccess;
 }
 
 int cairo_device_count(void) {

@@ -1,7 +1,8 @@
 // cairo_amd/csrc/capfmt_pixel.h -- the sample rules of the capture and 10-bit
 // layouts (include/cairo_amd.h, CAIRO_FMT_YUY2 / UYVY / P010; DESIGN.md
 // §4.16), as __host__ __device__ functions: the strips of pixfmt.hip and
-// cairo_frame_fold compile this one text.  It needs nothing but <stdint.h>.
+// cairo_frame_fold compile this one text.  It needs nothing but <stdint.h>
+// and pixel_common.h (the host + device macro and the register pin, pin8).
 //
 // fold takes a frame of one of the three layouts to the NV12 frame the codec
 // takes in its place, unfold takes an NV12 frame back.  Everything is integer.
@@ -10,45 +11,34 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define CAIRO_CAP_HD __host__ __device__ __forceinline__
-#else
-#define CAIRO_CAP_HD inline
-#endif
+#include "pixel_common.h"
 
 namespace cairo {
 
 constexpr int kFmtYuy2 = 8, kFmtUyvy = 9, kFmtP010 = 10;  // CAIRO_FMT_YUY2 / UYVY / P010
 
-// A folded sample in a register of its own before anything packs it into a
-// dword or a pair of half-words (a clamp or shift fused with the
-// packing corrupted the upper bytes of a packed dword on the device).
-CAIRO_CAP_HD uint32_t cap_pin(uint32_t r) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(r));
-#endif
-  return r;
-}
+// Every folded or unfolded sample is pinned (pin8) before anything packs it
+// into a dword or a pair of half-words.
 
 // Packed 4:2:2 fold: the 4:2:0 chroma sample between rows 2cy and 2cy + 1 is
 // the mean of their two 4:2:2 samples, halves rounded up.
-CAIRO_CAP_HD uint32_t cap_fold_chroma(uint32_t row0, uint32_t row1) { return cap_pin((row0 + row1 + 1u) >> 1); }
+CAIRO_HD uint32_t cap_fold_chroma(uint32_t row0, uint32_t row1) { return pin8((row0 + row1 + 1u) >> 1); }
 
 // P010 fold: the ten significant bits are the word's high ten, the low six are
 // ignored; to 8 bits by round to nearest, halves up, clamped to 255.
-CAIRO_CAP_HD uint32_t cap_fold_p010(uint32_t word) {
+CAIRO_HD uint32_t cap_fold_p010(uint32_t word) {
   const uint32_t s = (((word & 0xFFFFu) >> 6) + 2u) >> 2;
-  return cap_pin(s > 255u ? 255u : s);
+  return pin8(s > 255u ? 255u : s);
 }
 
 // P010 unfold: the 8-bit sample in the word's high byte, the low byte zero.
-CAIRO_CAP_HD uint32_t cap_unfold_p010(uint32_t s8) { return cap_pin((s8 & 255u) << 8); }
+CAIRO_HD uint32_t cap_unfold_p010(uint32_t s8) { return pin8((s8 & 255u) << 8); }
 
 // Byte offsets inside the 4 bytes of a pixel pair: YUY2 is Y0 U Y1 V, UYVY is
 // U Y0 V Y1.
-CAIRO_CAP_HD int cap_y_at(int fmt, int k) { return 2 * k + (fmt == kFmtUyvy ? 1 : 0); }  // luma column k
-CAIRO_CAP_HD int cap_u_at(int fmt, int j) { return 4 * j + (fmt == kFmtUyvy ? 0 : 1); }  // pair j
-CAIRO_CAP_HD int cap_v_at(int fmt, int j) { return 4 * j + (fmt == kFmtUyvy ? 2 : 3); }
+CAIRO_HD int cap_y_at(int fmt, int k) { return 2 * k + (fmt == kFmtUyvy ? 1 : 0); }  // luma column k
+CAIRO_HD int cap_u_at(int fmt, int j) { return 4 * j + (fmt == kFmtUyvy ? 0 : 1); }  // pair j
+CAIRO_HD int cap_v_at(int fmt, int j) { return 4 * j + (fmt == kFmtUyvy ? 2 : 3); }
 
 // The two maps as plain loops on buffers this code can address: what
 // cairo_frame_fold runs.  dir 0 reads the frame and writes the NV12 image

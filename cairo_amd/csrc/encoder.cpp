@@ -17,6 +17,7 @@
 #include "entropy.h"
 #include "evx_defs.h"
 #include "frame_io.h"
+#include "rgb_pixel.h"
 #include "stream_format.h"
 
 namespace evx {
@@ -28,13 +29,6 @@ constexpr uint16 kDefaultQuality = 8;      // EVX_DEFAULT_QUALITY_LEVEL, config.
 constexpr uint32 kPeriodicIntra = 3600;    // EVX_PERIODIC_INTRA_RATE, config.h:41
 
 int clip_quality(int q) { return q < 1 ? 1 : (q > 31 ? 31 : q); }
-
-// EVX_CONVERT_PIXEL_YUV_TO_RGB with saturate (convert.cpp:16-19; saturate
-// narrows to int16 before clipping, math.h:218-221).
-inline uint8 sat(int32 v) {
-  const int16 s = (int16)v;
-  return (uint8)(s < 0 ? 0 : (s > 255 ? 255 : s));
-}
 
 }  // namespace
 
@@ -134,14 +128,13 @@ class gpu_encoder : public evx1_encoder {
         return EVX_ERROR_HARDWAREFAIL;
       }
       for (uint32 j = 0; j < height_; j++)
-        for (uint32 i = 0; i < width_; i++) {  // convert.cpp:162-223
+        for (uint32 i = 0; i < width_; i++) {  // convert.cpp:162-223, the rule of rgb_pixel.h
           const int32 y = buf[(size_t)j * wa + i] - 16;
           const int32 u = buf[ny + (size_t)(j / 2) * (wa / 2) + i / 2] - 128;
           const int32 v = buf[ny + nc + (size_t)(j / 2) * (wa / 2) + i / 2] - 128;
           uint8 *p = out + ((size_t)j * width_ + i) * 3;
-          p[0] = sat((256 * y + 358 * v + 128) >> 8);
-          p[1] = sat((256 * y - 88 * u - 182 * v + 128) >> 8);
-          p[2] = sat((256 * y + 452 * u + 128) >> 8);
+          const cairo::Rgb8 c = cairo::yuv_to_rgb8(y, u, v);
+          p[0] = (uint8)c.r, p[1] = (uint8)c.g, p[2] = (uint8)c.b;
         }
       free(buf);
       return EVX_SUCCESS;

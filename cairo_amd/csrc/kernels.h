@@ -438,7 +438,7 @@ struct ConvertArgs {
   int sync_words;
 };
 // RGB -> YUV of every frame of the batch into its slot's source planes, plus
-// the views and sync area above (grid slice z = nframes).
+// the views and sync area above (grid slice z = nframes).  Defined in pixfmt.hip.
 hipError_t launch_convert_batch(const ConvertArgs& c, hipStream_t s);
 // The same launch when any of its frames is not tight RGB24 (pixfmt.hip):
 // every frame carries its format (CAIRO_FMT_*) and row pitch in bytes, and is
@@ -482,7 +482,7 @@ hipError_t engine_blocks_per_cu(int* n);
 hipError_t launch_unpack_granules(const EngineArgs& e, int j, PlaneSet dst, hipStream_t s);
 
 // convert_image YUV -> RGB (convert.cpp:16-19, 162-223) of plane set src into
-// RGB888 rgb (w x h, pitch 3*w).
+// RGB888 rgb (w x h, pitch 3*w).  Defined in pixfmt.hip.
 hipError_t launch_yuv_to_rgb(PlaneSet src, int wa, int w, int h, uint8_t* rgb, hipStream_t s);
 
 // Known-answer entry points: apply the device transform / quantizer code to

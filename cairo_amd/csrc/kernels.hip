@@ -1,7 +1,5 @@
 // cairo_amd/csrc/kernels.hip -- the EVX-1 encode hot path on gfx950 (CDNA4).
 //
-//   k_convert_batch  RGB888 -> planar YUV 4:2:0 int16, every frame of a
-//                    launch                                    convert.cpp:95-160
 //   k_engine         one persistent launch per batch of frames, pipelined
 //                    across frames, two pools of 256-thread workgroups:
 //     row helpers    inter search of their MB row (one wave per MB and
@@ -11,8 +9,9 @@
 //     row coders     intra search, classify, transform, VAQ, quantize,
 //                    reconstruct, left to right                encode.cpp:17-203,
 //                                                              decode.cpp:15-144
-//   k_yuv_to_rgb     the decoder's output conversion          convert.cpp:162-223
 //   k_kat_transform  known-answer entry of the transform chain (tests)
+// (The conversion kernels at its two ends, k_convert_batch and k_yuv_to_rgb,
+// are in pixfmt.hip.)
 //
 // All arithmetic is integer and restates the reference bit for bit (see
 // evx_defs.h for the helpers).  Searches evaluate candidates in parallel and
@@ -432,47 +431,6 @@ __device__ __forceinline__ int dequeue(int32_t* ticket, int* lds_slot) {
     *lds_slot = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   return *lds_slot;
-}
-
-// ---------------------------------------------------------------------------
-// K0: RGB888 -> YUV 4:2:0 int16 (convert.cpp:11-14, 30-73, 95-160)
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void k_convert_batch(ConvertArgs e) {
-  if ((int)blockIdx.z == e.nframes) {
-    // the launch's frame views (mapped host memory -> device) and zeroed sync
-    // area, spread over the slice's blocks
-    const int nb = gridDim.x * gridDim.y, t = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-    for (int k = t; k < e.fa_chunks; k += nb * 256) e.fa_dev[k] = e.fa_host[k];
-    for (int k = t; k < e.sync_words; k += nb * 256) e.sync[k] = 0;
-    return;
-  }
-  const uint8_t* rgb = e.rgb[blockIdx.z];
-  const int qx = blockIdx.x * 256 + threadIdx.x;  // quad column
-  const int qy = blockIdx.y;                      // quad row
-  if (qx >= (e.w >> 1) || !rgb) return;
-  const PlaneSet in = e.in[blockIdx.z];
-  int su = 0, sv = 0;
-#pragma unroll
-  for (int dy = 0; dy < 2; dy++) {
-    const uint8_t* p = rgb + ((size_t)(2 * qy + dy) * e.w + 2 * qx) * 3;
-    int16_t* y = in.y + (size_t)(2 * qy + dy) * e.wa + 2 * qx;
-#pragma unroll
-    for (int dx = 0; dx < 2; dx++) {
-      int r = p[3 * dx], g = p[3 * dx + 1], b = p[3 * dx + 2];
-      y[dx] = (int16_t)(((77 * r + 150 * g + 29 * b + 128) >> 8) + 16);
-      su = (int16_t)(su + (((-43 * r - 85 * g + 128 * b + 128) / 256) + 128));
-      sv = (int16_t)(sv + (((128 * r - 107 * g - 21 * b + 128) / 256) + 128));
-    }
-  }
-  in.u[(size_t)qy * (e.wa >> 1) + qx] = (int16_t)((su + 2) >> 2);
-  in.v[(size_t)qy * (e.wa >> 1) + qx] = (int16_t)((sv + 2) >> 2);
-}
-
-hipError_t launch_convert_batch(const ConvertArgs& e, hipStream_t s) {
-  dim3 grid((e.w / 2 + 255) / 256, e.h / 2, e.nframes + 1);
-  hipLaunchKernelGGL(k_convert_batch, grid, dim3(256), 0, s, e);
-  return hipGetLastError();
 }
 
 // Biased 16-bit storage (v ^ 0x8000): unsigned order equals signed order.
@@ -3367,38 +3325,6 @@ hipError_t launch_engine(const EngineArgs& e, hipStream_t s) {
     hipLaunchKernelGGL(k_engine<true>, dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
   else
     hipLaunchKernelGGL(k_engine<false>, dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
-  return hipGetLastError();
-}
-
-
-// ---------------------------------------------------------------------------
-// convert_image YUV -> RGB (convert.cpp:16-19, 75-93, 162-223): one thread per
-// horizontal pixel pair; saturate narrows to int16 before clipping
-// (math.h:218-221).  The crop is min(W, Wa) x min(H, Ha) = W x H.
-// ---------------------------------------------------------------------------
-
-__device__ __forceinline__ uint8_t sat8(int32_t v) {
-  const int16_t s = (int16_t)v;
-  return (uint8_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
-}
-
-__global__ __launch_bounds__(256) void k_yuv_to_rgb(PlaneSet src, int wa, int w, int h, uint8_t* rgb) {
-  const int x2 = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (2 * x2 >= w) return;
-  const int u = src.u[(size_t)(y >> 1) * (wa >> 1) + x2] - 128;
-  const int v = src.v[(size_t)(y >> 1) * (wa >> 1) + x2] - 128;
-  uint8_t* o = rgb + ((size_t)y * w + 2 * x2) * 3;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int yy = src.y[(size_t)y * wa + 2 * x2 + k] - 16;
-    o[3 * k] = sat8((256 * yy + 358 * v + 128) >> 8);
-    o[3 * k + 1] = sat8((256 * yy - 88 * u - 182 * v + 128) >> 8);
-    o[3 * k + 2] = sat8((256 * yy + 452 * u + 128) >> 8);
-  }
-}
-
-hipError_t launch_yuv_to_rgb(PlaneSet src, int wa, int w, int h, uint8_t* rgb, hipStream_t s) {
-  hipLaunchKernelGGL(k_yuv_to_rgb, dim3((w / 2 + 255) / 256, h), dim3(256), 0, s, src, wa, w, h, rgb);
   return hipGetLastError();
 }
 

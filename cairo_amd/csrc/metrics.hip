@@ -17,12 +17,15 @@
 //     frame's result (mapped pinned host memory inside a context).
 // No floating-point atomics and no order that depends on timing: the same
 // input gives the same bits.  No fast-math flag: the fp64 division is IEEE.
+// The plane loads are strip_access.h's load_i16<8>, the clamp pixel_common.h's;
+// the status values, fail() and the KAT's device buffers are hip_status.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdio>
-
+#include "hip_status.h"
 #include "metrics.h"
+#include "pixel_common.h"
+#include "strip_access.h"
 
 namespace cairo {
 
@@ -33,23 +36,6 @@ constexpr int kBlocksX = kMetTileW / 4, kBlocksY = kMetTileH / 4;  // 32 x 16 bl
 constexpr int kUnitsX = kBlocksX / 2 + 1;  // units of 2 blocks per row, the last one holds the halo column
 constexpr int kUnitsY = kBlocksY + 1;      // block rows, the last one is the halo row
 constexpr int kSsimC1 = 416, kSsimC2 = 235963;
-
-__device__ __forceinline__ int clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-// The first n of 8 plane elements at p: one 16-byte access when all are
-// wanted and p is aligned to it; elements from n on read as 0 and nothing
-// beyond the n-th is touched.
-__device__ __forceinline__ void load8(const int16_t* p, int n, int (&v)[8]) {
-  if (n == 8 && ((uintptr_t)p & 15) == 0) {
-    const uint4 q = *(const uint4*)p;
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = (int)(int16_t)(w[k >> 1] >> (16 * (k & 1)));
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = k < n ? (int)p[k] : 0;
-  }
-}
 
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 #pragma unroll
@@ -104,8 +90,8 @@ __global__ __launch_bounds__(kMetThreads) void k_metrics_tiles(MetricsArgs m) {
         if (y + r >= ph) break;
         const size_t o = (size_t)(y + r) * pitch + x;
         int va[8], vb[8];
-        load8(pa + o, n, va);
-        load8(pb + o, n, vb);
+        load_i16<8>(pa + o, n, va);
+        load_i16<8>(pb + o, n, vb);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
           const int a = k < n ? clamp8(va[k] - off) : 0, b = k < n ? clamp8(vb[k] - off) : 0;
@@ -181,14 +167,6 @@ __global__ __launch_bounds__(192) void k_metrics_finish(MetricsArgs m) {
   }
 }
 
-constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
-
-int fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return kSuccess;
-  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
-  return kHardwareFail;
-}
-
 }  // namespace
 
 hipError_t launch_metrics(const MetricsArgs& m, hipStream_t s) {
@@ -221,37 +199,24 @@ int cairo_kat_metrics(uint32_t w, uint32_t h, uint32_t pitch_elems, const int16_
   int r = fail(hipSetDevice(device), "hipSetDevice");
   if (r) return r;
   const size_t ny = (size_t)pitch_elems * h, nc = (size_t)(pitch_elems / 2) * (h / 2), ne = ny + 2 * nc;
-  const size_t np = (size_t)3 * metrics_tiles((int)w, (int)h);
-  int16_t* dp = nullptr;  // a: y | u | v, then b
-  MetricsPartial* part = nullptr;
-  cairo_frame_metrics* dout = nullptr;
-  if ((r = fail(hipMalloc(&dp, 2 * ne * 2), "malloc")) || (r = fail(hipMalloc(&part, np * sizeof(MetricsPartial)), "malloc")) ||
-      (r = fail(hipMalloc(&dout, sizeof(*dout)), "malloc")))
-    goto done;
-  {
-    MetricsArgs m{};
-    m.w = (int)w, m.h = (int)h, m.pitch = (int)pitch_elems, m.nframes = 1;
-    m.flags = CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM;
-    m.a[0].y = dp, m.a[0].u = dp + ny, m.a[0].v = dp + ny + nc;
-    m.b[0].y = dp + ne, m.b[0].u = dp + ne + ny, m.b[0].v = dp + ne + ny + nc;
-    m.slot[0] = 0;
-    m.part = part;
-    m.out = dout;
-    if ((r = fail(hipMemcpy(m.a[0].y, a_y, ny * 2, hipMemcpyHostToDevice), "h2d")) ||
-        (r = fail(hipMemcpy(m.a[0].u, a_u, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-        (r = fail(hipMemcpy(m.a[0].v, a_v, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-        (r = fail(hipMemcpy(m.b[0].y, b_y, ny * 2, hipMemcpyHostToDevice), "h2d")) ||
-        (r = fail(hipMemcpy(m.b[0].u, b_u, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-        (r = fail(hipMemcpy(m.b[0].v, b_v, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-        (r = fail(launch_metrics(m, nullptr), "k_metrics")) || (r = fail(hipDeviceSynchronize(), "sync")) ||
-        (r = fail(hipMemcpy(out, dout, sizeof(*out), hipMemcpyDeviceToHost), "d2h")))
-      goto done;
-  }
-done:
-  (void)hipFree(dp);
-  (void)hipFree(part);
-  (void)hipFree(dout);
-  return r;
+  KatBuffer dp, part, dout;  // dp: a's y | u | v, then b's
+  if ((r = dp.alloc(2 * ne * 2)) || (r = part.alloc((size_t)3 * metrics_tiles((int)w, (int)h) * sizeof(MetricsPartial))) ||
+      (r = dout.alloc(sizeof(*out))))
+    return r;
+  MetricsArgs m{};
+  m.w = (int)w, m.h = (int)h, m.pitch = (int)pitch_elems, m.nframes = 1;
+  m.flags = CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM;
+  m.a[0].y = dp.as<int16_t>(), m.a[0].u = m.a[0].y + ny, m.a[0].v = m.a[0].u + nc;
+  m.b[0].y = m.a[0].y + ne, m.b[0].u = m.b[0].y + ny, m.b[0].v = m.b[0].u + nc;
+  m.slot[0] = 0;
+  m.part = part.as<MetricsPartial>();
+  m.out = dout.as<cairo_frame_metrics>();
+  if ((r = dp.upload(a_y, ny * 2)) || (r = dp.upload(a_u, nc * 2, ny * 2)) || (r = dp.upload(a_v, nc * 2, (ny + nc) * 2)) ||
+      (r = dp.upload(b_y, ny * 2, ne * 2)) || (r = dp.upload(b_u, nc * 2, (ne + ny) * 2)) ||
+      (r = dp.upload(b_v, nc * 2, (ne + ny + nc) * 2)) || (r = kat_run(launch_metrics(m, nullptr), "k_metrics")) ||
+      (r = dout.download(out, sizeof(*out))))
+    return r;
+  return kSuccess;
 }
 
 }  // extern "C"

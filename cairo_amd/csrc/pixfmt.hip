@@ -1,14 +1,17 @@
-// cairo_amd/csrc/pixfmt.hip -- pixel formats at the codec's edges: BGR24,
-// I420, NV12, YUY2, UYVY and P010 frames (and RGB24 with a row pitch) into the
-// int16 4:2:0 source planes, and ring-slot planes out into any of the formats.
+// cairo_amd/csrc/pixfmt.hip -- every conversion kernel at the codec's edges:
+// frames into the int16 4:2:0 source planes, and ring-slot planes out into
+// frames.  The sample rules are headers shared with the host (rgb_pixel.h: the
+// codec's own RGB <-> YUV; capfmt_pixel.h; pixel_common.h), the strip accesses
+// are strip_access.h.
 //
-// The default launch (every frame tight RGB24) keeps k_convert_batch, and
-// cairo_ctx_decode_frame keeps k_yuv_to_rgb (kernels.hip): both are measured
-// beside a running engine launch.  The kernels here run
-// whenever a launch holds any other layout.
+// The default launch (every frame tight RGB24) runs k_convert_batch, and
+// cairo_ctx_decode_frame runs k_yuv_to_rgb: both are measured beside a running
+// engine launch and keep their work split and their
+// code (§4.17).  The strip kernels run whenever a launch holds any other
+// layout: BGR24, I420, NV12, YUY2, UYVY, P010, and RGB24 with a row pitch.
 //
-// Work split of both kernels: one thread owns a strip of 8 luma columns by 2
-// rows (4 chroma samples per plane), so that a strip's Y rows are one 16-byte
+// Work split of both strip kernels: one thread owns a strip of 8 luma columns
+// by 2 rows (4 chroma samples per plane): a strip's Y rows are one 16-byte
 // plane access each and its 8-bit side is whole dwords.  A strip falls back to
 // byte accesses where its row start is not aligned or where it is cut by the
 // right edge; nothing outside width x height is read or written on either
@@ -19,18 +22,19 @@
 // packed 4:2:2 layouts, 16 of each Y row and 16 of the UV row for P010.
 //
 // The YUV frames carry a colour description (cairo_amd.h CAIRO_RANGE_*,
-// CAIRO_MATRIX_*; YUY2, UYVY and P010: of their NV12).  Both strip functions take its mode as a
-// template parameter, chosen once per workgroup like the format: identity (the
-// codec's own space: the code as it was), diagonal (LIMITED with BT601: no
-// chroma term in the luma) and full.
+// CAIRO_MATRIX_*; YUY2, UYVY and P010: of their NV12).  Both
+// strip functions take its mode as a template parameter, chosen once per
+// workgroup like the format: identity (the codec's own space: the code as it
+// was), diagonal (LIMITED with BT601: no chroma term in the luma) and full.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdio>
-
 #include "../../include/cairo_amd.h"
 #include "capfmt_pixel.h"
+#include "hip_status.h"
 #include "kernels.h"
+#include "rgb_pixel.h"
+#include "strip_access.h"
 
 namespace cairo {
 
@@ -39,35 +43,13 @@ namespace {
 constexpr int kStrip = 8;         // luma columns per thread
 constexpr int kFmtThreads = 128;  // a workgroup spans 1024 luma columns of one row pair
 
-// saturate narrows to int16 first (math.h:218-221).  The result is pinned to a
-// 32-bit register of its own before it is shifted into its dword: left to
-// itself the compiler fuses shift, clamp and byte packing into
-// v_ashr_pk_u8_i32 and 16-bit ops, and bytes 2 and 3 of a packed dword then
-// carried bits of an unclamped neighbour on the device (the same source is
-// right on a CPU; the KAT's output side caught it).
-__device__ __forceinline__ uint32_t sat8(int32_t v) {
-  const int s = (int)(int16_t)v;
-  uint32_t r = (uint32_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(r));
-#endif
-  return r;
-}
-__device__ __forceinline__ uint32_t clamp8(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
 // Modes of a colour description index (kernels.h color_index).
 constexpr int kColorIdentity = 0, kColorDiagonal = 1, kColorFull = 2;
 constexpr int kColorShift = 14, kColorHalf = 1 << (kColorShift - 1);
 
-// A sample of a colour map: one rounding, clamped to 0..255 and, like sat8,
-// pinned to a register of its own before anything packs it.
-__device__ __forceinline__ uint32_t color8(int32_t acc) {
-  uint32_t r = clamp8(acc >> kColorShift);
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(r));
-#endif
-  return r;
-}
+// A sample of a colour map: one rounding, clamped to 0..255 and pinned before
+// anything packs it.
+__device__ __forceinline__ uint32_t color8(int32_t acc) { return pin8(clamp8(acc >> kColorShift)); }
 
 // The map of one strip on its 8-bit samples, in place: y8[dy][k] with the
 // chroma sample k >> 1, then the chroma samples themselves (which never depend
@@ -99,66 +81,6 @@ __device__ __forceinline__ void color_strip(const ColorMap& m, int (&y8)[2][kStr
   }
 }
 
-// Byte k of a little-endian dword array.
-template <int W>
-__device__ __forceinline__ int byte_of(const uint32_t (&w)[W], int k) {
-  return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
-}
-
-// The unsigned integer of UNIT bytes: the narrow access of load_bytes and
-// store_bytes.
-template <int UNIT>
-struct Narrow {
-  typedef uint8_t type;
-};
-template <>
-struct Narrow<2> {
-  typedef uint16_t type;
-};
-
-// The first n of N bytes at p (N a multiple of 4) into dwords: dword loads
-// when all N are wanted and p is 4-byte aligned, else loads of UNIT bytes of
-// the n valid ones (the rest read as 0).  UNIT 2: p is 2-byte aligned and n
-// even (16-bit samples).
-template <int N, int UNIT = 1>
-__device__ __forceinline__ void load_bytes(const uint8_t* p, int n, uint32_t (&w)[N / 4]) {
-  static_assert(UNIT == 1 || UNIT == 2, "byte or half-word accesses");
-  if (n == N && ((uintptr_t)p & 3) == 0) {
-    const uint32_t* q = (const uint32_t*)p;
-#pragma unroll
-    for (int k = 0; k < N / 4; k++) w[k] = q[k];
-  } else {
-    const typename Narrow<UNIT>::type* q = (const typename Narrow<UNIT>::type*)p;
-#pragma unroll
-    for (int k = 0; k < N / 4; k++) w[k] = 0;
-#pragma unroll
-    for (int k = 0; k < N; k += UNIT)
-      if (k < n) w[k >> 2] |= (uint32_t)q[k / UNIT] << (8 * (k & 3));
-  }
-}
-
-// The first n of N bytes held in dwords to p; bytes from n on are not written.
-template <int N, int UNIT = 1>
-__device__ __forceinline__ void store_bytes(uint8_t* p, int n, const uint32_t (&w)[N / 4]) {
-  static_assert(UNIT == 1 || UNIT == 2, "byte or half-word accesses");
-  if (n == N && ((uintptr_t)p & 3) == 0) {
-    uint32_t* q = (uint32_t*)p;
-#pragma unroll
-    for (int k = 0; k < N / 4; k++) q[k] = w[k];
-  } else {
-    typename Narrow<UNIT>::type* q = (typename Narrow<UNIT>::type*)p;
-#pragma unroll
-    for (int k = 0; k < N; k += UNIT)
-      if (k < n) q[k / UNIT] = (typename Narrow<UNIT>::type)(w[k >> 2] >> (8 * (k & 3)));
-  }
-}
-
-// Half-word k of a little-endian dword array.
-template <int W>
-__device__ __forceinline__ uint32_t half_of(const uint32_t (&w)[W], int k) {
-  return (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-}
-
 static_assert(kFmtYuy2 == CAIRO_FMT_YUY2 && kFmtUyvy == CAIRO_FMT_UYVY && kFmtP010 == CAIRO_FMT_P010,
               "capfmt_pixel.h names the header's values");
 
@@ -169,49 +91,18 @@ constexpr bool fmt_is_yuv(int fmt) {
          fmt == CAIRO_FMT_P010;
 }
 
-// The first n of N plane elements (N = 8: 16 bytes, N = 4: 8 bytes) at p as
-// one vector access when all are wanted and p is aligned to it.
-template <int N>
-__device__ __forceinline__ void store_i16(int16_t* p, int n, const int (&v)[N]) {
-  static_assert(N == 8 || N == 4, "a 16-byte or an 8-byte plane access");
-  if (n == N && ((uintptr_t)p & (2 * N - 1)) == 0) {
-    uint32_t w[N / 2];
-#pragma unroll
-    for (int k = 0; k < N / 2; k++) w[k] = ((uint32_t)v[2 * k] & 0xFFFFu) | ((uint32_t)v[2 * k + 1] << 16);
-    if constexpr (N == 8)
-      *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
-    else
-      *(uint2*)p = make_uint2(w[0], w[1]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; k++)
-      if (k < n) p[k] = (int16_t)v[k];
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void load_i16(const int16_t* p, int n, int (&v)[N]) {
-  static_assert(N == 8 || N == 4, "a 16-byte or an 8-byte plane access");
-  if (n == N && ((uintptr_t)p & (2 * N - 1)) == 0) {
-    uint32_t w[N / 2];
-    if constexpr (N == 8) {
-      const uint4 q = *(const uint4*)p;
-      w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-    } else {
-      const uint2 q = *(const uint2*)p;
-      w[0] = q.x, w[1] = q.y;
-    }
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = (int)(int16_t)(w[k >> 1] >> (16 * (k & 1)));
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = k < n ? (int)p[k] : 0;
-  }
+// Slice z == nframes of a convert launch, nthreads threads a workgroup: the
+// launch's frame views (mapped host memory -> device) and the zeroed sync area,
+// spread over the slice's blocks.
+__device__ __forceinline__ void launch_prologue(const ConvertArgs& e, int nthreads) {
+  const int nb = gridDim.x * gridDim.y, t = (blockIdx.y * gridDim.x + blockIdx.x) * nthreads + threadIdx.x;
+  for (int k = t; k < e.fa_chunks; k += nb * nthreads) e.fa_dev[k] = e.fa_host[k];
+  for (int k = t; k < e.sync_words; k += nb * nthreads) e.sync[k] = 0;
 }
 
 // ---------------------------------------------------------------------------
 // Input side: strip sx of row pair qy of one frame -> its source planes.
-// RGB24 / BGR24: the arithmetic of k_convert_batch (convert.cpp:11-14, 30-73).
+// RGB24 / BGR24: the rule of k_convert_batch (rgb_pixel.h).
 // I420 / NV12: the codec's own full-range BT.601 samples, Y + 16, U, V; under
 // a colour description, the same rule on the mapped samples.
 // YUY2 / UYVY / P010: the NV12 rule on the folded samples (capfmt_pixel.h).
@@ -234,13 +125,14 @@ __device__ __forceinline__ void convert_strip(const uint8_t* frame, uint32_t pit
       for (int k = 0; k < kStrip; k++) {
         const int c0 = byte_of(px, 3 * k), g = byte_of(px, 3 * k + 1), c2 = byte_of(px, 3 * k + 2);
         const int r = FMT == CAIRO_FMT_RGB24 ? c0 : c2, b = FMT == CAIRO_FMT_RGB24 ? c2 : c0;
+        // rgb_luma(r, g, b) written out: the call changed this kernel's code and its BGR24 leg
         yv[dy][k] = ((77 * r + 150 * g + 29 * b + 128) >> 8) + 16;
-        su[k >> 1] += ((-43 * r - 85 * g + 128 * b + 128) / 256) + 128;
-        sv[k >> 1] += ((128 * r - 107 * g - 21 * b + 128) / 256) + 128;
+        su[k >> 1] += rgb_chroma_u(r, g, b);
+        sv[k >> 1] += rgb_chroma_v(r, g, b);
       }
     }
 #pragma unroll
-    for (int k = 0; k < kStrip / 2; k++) uv[k] = (su[k] + 2) >> 2, vv[k] = (sv[k] + 2) >> 2;
+    for (int k = 0; k < kStrip / 2; k++) uv[k] = chroma_mean4(su[k]), vv[k] = chroma_mean4(sv[k]);
   } else {
     constexpr int ybase = MODE == kColorIdentity ? 16 : 0;
     if constexpr (FMT == CAIRO_FMT_YUY2 || FMT == CAIRO_FMT_UYVY) {
@@ -321,14 +213,12 @@ __device__ __forceinline__ void convert_strip_col(int col, const uint8_t* frame,
     convert_strip<FMT, kColorFull>(frame, pitch, in, w, h, wa, sx, qy, m);
 }
 
-// Same grid convention as k_convert_batch: slice z < nframes converts frame z
+// Grid convention of both convert kernels: slice z < nframes converts frame z
 // (a null source: a decoded frame, nothing to convert), slice z == nframes
 // copies the launch's frame views to the device and zeroes its sync area.
 __global__ __launch_bounds__(kFmtThreads) void k_convert_fmt_batch(ConvertFmtArgs e) {
   if ((int)blockIdx.z == e.c.nframes) {
-    const int nb = gridDim.x * gridDim.y, t = (blockIdx.y * gridDim.x + blockIdx.x) * kFmtThreads + threadIdx.x;
-    for (int k = t; k < e.c.fa_chunks; k += nb * kFmtThreads) e.c.fa_dev[k] = e.c.fa_host[k];
-    for (int k = t; k < e.c.sync_words; k += nb * kFmtThreads) e.c.sync[k] = 0;
+    launch_prologue(e.c, kFmtThreads);
     return;
   }
   const uint8_t* frame = e.c.rgb[blockIdx.z];
@@ -351,7 +241,7 @@ __global__ __launch_bounds__(kFmtThreads) void k_convert_fmt_batch(ConvertFmtArg
 
 // ---------------------------------------------------------------------------
 // Output side: strip sx of row pair qy of a plane set -> the pitched frame.
-// RGB24 / BGR24: the arithmetic of k_yuv_to_rgb (convert.cpp:16-19, 162-223).
+// RGB24 / BGR24: the rule of k_yuv_to_rgb (rgb_pixel.h), each byte pinned.
 // I420 / NV12: clamp(Y - 16), clamp(U), clamp(V) of the int16 samples; under a
 // colour description those 8-bit samples are then mapped.
 // YUY2 / UYVY / P010: the unfold of those NV12 samples (capfmt_pixel.h).
@@ -375,11 +265,8 @@ __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w,
       uint32_t px[6] = {};
 #pragma unroll
       for (int k = 0; k < kStrip; k++) {
-        const int yy = yv[dy][k] - 16, u = uv[k >> 1] - 128, v = vv[k >> 1] - 128;
-        const uint32_t r = sat8((256 * yy + 358 * v + 128) >> 8);
-        const uint32_t g = sat8((256 * yy - 88 * u - 182 * v + 128) >> 8);
-        const uint32_t b = sat8((256 * yy + 452 * u + 128) >> 8);
-        const uint32_t c0 = FMT == CAIRO_FMT_RGB24 ? r : b, c2 = FMT == CAIRO_FMT_RGB24 ? b : r;
+        const Rgb8 c = yuv_to_rgb8<true>(yv[dy][k] - 16, uv[k >> 1] - 128, vv[k >> 1] - 128);
+        const uint32_t g = c.g, c0 = FMT == CAIRO_FMT_RGB24 ? c.r : c.b, c2 = FMT == CAIRO_FMT_RGB24 ? c.b : c.r;
         px[(3 * k) >> 2] |= c0 << (8 * ((3 * k) & 3));
         px[(3 * k + 1) >> 2] |= g << (8 * ((3 * k + 1) & 3));
         px[(3 * k + 2) >> 2] |= c2 << (8 * ((3 * k + 2) & 3));
@@ -403,12 +290,12 @@ __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w,
     if constexpr (FMT == CAIRO_FMT_YUY2 || FMT == CAIRO_FMT_UYVY) {
       uint32_t cu[kStrip / 2], cv[kStrip / 2];  // both rows of the pair carry the same chroma bytes
 #pragma unroll
-      for (int k = 0; k < kStrip / 2; k++) cu[k] = cap_pin(ub(k)), cv[k] = cap_pin(vb(k));
+      for (int k = 0; k < kStrip / 2; k++) cu[k] = pin8(ub(k)), cv[k] = pin8(vb(k));
 #pragma unroll
       for (int dy = 0; dy < 2; dy++) {
         uint32_t px[4] = {};  // 4 pixel pairs
 #pragma unroll
-        for (int k = 0; k < kStrip; k++) px[k >> 1] |= cap_pin(yb(dy, k)) << (8 * (cap_y_at(FMT, k) & 3));
+        for (int k = 0; k < kStrip; k++) px[k >> 1] |= pin8(yb(dy, k)) << (8 * (cap_y_at(FMT, k) & 3));
 #pragma unroll
         for (int k = 0; k < kStrip / 2; k++)
           px[k] |= (cu[k] << (8 * (cap_u_at(FMT, k) & 3))) | (cv[k] << (8 * (cap_v_at(FMT, k) & 3)));
@@ -419,13 +306,13 @@ __device__ __forceinline__ void planes_strip(const PlaneSet& src, int sp, int w,
       for (int dy = 0; dy < 2; dy++) {
         uint32_t py[4] = {};  // 8 words
 #pragma unroll
-        for (int k = 0; k < kStrip; k++) py[k >> 1] |= cap_unfold_p010(cap_pin(yb(dy, k))) << (16 * (k & 1));
+        for (int k = 0; k < kStrip; k++) py[k >> 1] |= cap_unfold_p010(pin8(yb(dy, k))) << (16 * (k & 1));
         store_bytes<16, 2>(dst + (size_t)(2 * qy + dy) * pitch + 2 * x0, 2 * n, py);
       }
       uint32_t puv[4] = {};  // 4 U, V word pairs
 #pragma unroll
       for (int k = 0; k < kStrip / 2; k++)
-        puv[k] = cap_unfold_p010(cap_pin(ub(k))) | (cap_unfold_p010(cap_pin(vb(k))) << 16);
+        puv[k] = cap_unfold_p010(pin8(ub(k))) | (cap_unfold_p010(pin8(vb(k))) << 16);
       store_bytes<16, 2>(dst + (size_t)pitch * h + (size_t)qy * pitch + 2 * x0, 2 * n, puv);
     } else {
 #pragma unroll
@@ -497,25 +384,72 @@ constexpr ColorMap kColorTable[2][kColorMaps] = {
      {16384, -1936, -3485, 16689, 1878, 1230, 16799, 0},
      {14071, -1663, -2993, 14660, 1650, 1080, 14757, 16}}};
 
-bool color_known(int range, int matrix) {
-  return (range == CAIRO_RANGE_FULL || range == CAIRO_RANGE_LIMITED) &&
-         (matrix == CAIRO_MATRIX_BT601 || matrix == CAIRO_MATRIX_BT709);
-}
-
-constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
-
-int fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return kSuccess;
-  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
-  return kHardwareFail;
-}
-
 dim3 strip_grid(int w, int h, int slices) {
   const int strips = (w + kStrip - 1) / kStrip;
   return dim3((strips + kFmtThreads - 1) / kFmtThreads, h / 2, slices);
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// The default input path, tight RGB888 -> YUV 4:2:0 int16 (convert.cpp:11-14,
+// 30-73, 95-160): one thread per 2 x 2 quad, 256 quad columns a workgroup.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_convert_batch(ConvertArgs e) {
+  if ((int)blockIdx.z == e.nframes) {
+    launch_prologue(e, 256);
+    return;
+  }
+  const uint8_t* rgb = e.rgb[blockIdx.z];
+  const int qx = blockIdx.x * 256 + threadIdx.x;  // quad column
+  const int qy = blockIdx.y;                      // quad row
+  if (qx >= (e.w >> 1) || !rgb) return;
+  const PlaneSet in = e.in[blockIdx.z];
+  int su = 0, sv = 0;  // (through int16_t as the reference adds them: rgb_pixel.h)
+#pragma unroll
+  for (int dy = 0; dy < 2; dy++) {
+    const uint8_t* p = rgb + ((size_t)(2 * qy + dy) * e.w + 2 * qx) * 3;
+    int16_t* y = in.y + (size_t)(2 * qy + dy) * e.wa + 2 * qx;
+#pragma unroll
+    for (int dx = 0; dx < 2; dx++) {
+      int r = p[3 * dx], g = p[3 * dx + 1], b = p[3 * dx + 2];
+      y[dx] = (int16_t)rgb_luma(r, g, b);
+      su = (int16_t)(su + rgb_chroma_u(r, g, b));
+      sv = (int16_t)(sv + rgb_chroma_v(r, g, b));
+    }
+  }
+  in.u[(size_t)qy * (e.wa >> 1) + qx] = (int16_t)chroma_mean4(su);
+  in.v[(size_t)qy * (e.wa >> 1) + qx] = (int16_t)chroma_mean4(sv);
+}
+
+hipError_t launch_convert_batch(const ConvertArgs& e, hipStream_t s) {
+  dim3 grid((e.w / 2 + 255) / 256, e.h / 2, e.nframes + 1);
+  hipLaunchKernelGGL(k_convert_batch, grid, dim3(256), 0, s, e);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The default output path, convert_image YUV -> RGB (convert.cpp:16-19, 75-93,
+// 162-223): one thread per horizontal pixel pair.  The crop is
+// min(W, Wa) x min(H, Ha) = W x H.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_yuv_to_rgb(PlaneSet src, int wa, int w, int h, uint8_t* rgb) {
+  const int x2 = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (2 * x2 >= w) return;
+  const int u = src.u[(size_t)(y >> 1) * (wa >> 1) + x2] - 128;
+  const int v = src.v[(size_t)(y >> 1) * (wa >> 1) + x2] - 128;
+  uint8_t* o = rgb + ((size_t)y * w + 2 * x2) * 3;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const Rgb8 c = yuv_to_rgb8(src.y[(size_t)y * wa + 2 * x2 + k] - 16, u, v);
+    o[3 * k] = (uint8_t)c.r, o[3 * k + 1] = (uint8_t)c.g, o[3 * k + 2] = (uint8_t)c.b;
+  }
+}
+
+hipError_t launch_yuv_to_rgb(PlaneSet src, int wa, int w, int h, uint8_t* rgb, hipStream_t s) {
+  hipLaunchKernelGGL(k_yuv_to_rgb, dim3((w / 2 + 255) / 256, h), dim3(256), 0, s, src, wa, w, h, rgb);
+  return hipGetLastError();
+}
 
 hipError_t launch_convert_fmt_batch(const ConvertFmtArgs& e, hipStream_t s) {
   ConvertFmtArgs a = e;
@@ -593,42 +527,29 @@ int cairo_kat_convert_color(int dir, int fmt, int range, int matrix, uint32_t w,
   int r = fail(hipSetDevice(device), "hipSetDevice");
   if (r) return r;
   const size_t ny = (size_t)w * h, nc = (size_t)(w / 2) * (h / 2);
-  uint8_t* df = nullptr;
-  int16_t* dp = nullptr;  // y | u | v, tight: w and w / 2 elements per row
-  if ((r = fail(hipMalloc(&df, bytes), "malloc")) || (r = fail(hipMalloc(&dp, (ny + 2 * nc) * 2), "malloc"))) goto done;
-  {
-    PlaneSet p;
-    p.y = dp, p.u = dp + ny, p.v = dp + ny + nc;
-    if (dir == 0) {
-      ConvertFmtArgs a{};
-      a.c.w = (int)w, a.c.h = (int)h, a.c.wa = (int)w, a.c.nframes = 1;
-      a.c.rgb[0] = df;
-      a.c.in[0] = p;
-      a.fmt[0] = (uint8_t)fmt;
-      a.pitch[0] = pitch;
-      a.col[0] = (uint8_t)col;
-      if ((r = fail(hipMemcpy(df, frame, bytes, hipMemcpyHostToDevice), "h2d")) ||
-          (r = fail(launch_convert_fmt_batch(a, nullptr), "k_convert_fmt_batch")) ||
-          (r = fail(hipDeviceSynchronize(), "sync")) ||
-          (r = fail(hipMemcpy(y, p.y, ny * 2, hipMemcpyDeviceToHost), "d2h")) ||
-          (r = fail(hipMemcpy(u, p.u, nc * 2, hipMemcpyDeviceToHost), "d2h")) ||
-          (r = fail(hipMemcpy(v, p.v, nc * 2, hipMemcpyDeviceToHost), "d2h")))
-        goto done;
-    } else {
-      if ((r = fail(hipMemcpy(df, frame, bytes, hipMemcpyHostToDevice), "h2d")) ||
-          (r = fail(hipMemcpy(p.y, y, ny * 2, hipMemcpyHostToDevice), "h2d")) ||
-          (r = fail(hipMemcpy(p.u, u, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-          (r = fail(hipMemcpy(p.v, v, nc * 2, hipMemcpyHostToDevice), "h2d")) ||
-          (r = fail(launch_planes_to_fmt(p, (int)w, (int)w, (int)h, fmt, pitch, df, col, nullptr), "k_planes_to_fmt")) ||
-          (r = fail(hipDeviceSynchronize(), "sync")) ||
-          (r = fail(hipMemcpy(frame, df, bytes, hipMemcpyDeviceToHost), "d2h")))
-        goto done;
-    }
+  KatBuffer df, dp;  // the frame; y | u | v, tight: w and w / 2 elements per row
+  if ((r = df.alloc(bytes)) || (r = dp.alloc((ny + 2 * nc) * 2)) || (r = df.upload(frame, bytes))) return r;
+  PlaneSet p;
+  p.y = dp.as<int16_t>(), p.u = p.y + ny, p.v = p.u + nc;
+  if (dir == 0) {
+    ConvertFmtArgs a{};
+    a.c.w = (int)w, a.c.h = (int)h, a.c.wa = (int)w, a.c.nframes = 1;
+    a.c.rgb[0] = df.as<uint8_t>();
+    a.c.in[0] = p;
+    a.fmt[0] = (uint8_t)fmt;
+    a.pitch[0] = pitch;
+    a.col[0] = (uint8_t)col;
+    if ((r = kat_run(launch_convert_fmt_batch(a, nullptr), "k_convert_fmt_batch")) || (r = dp.download(y, ny * 2)) ||
+        (r = dp.download(u, nc * 2, ny * 2)) || (r = dp.download(v, nc * 2, (ny + nc) * 2)))
+      return r;
+  } else {
+    if ((r = dp.upload(y, ny * 2)) || (r = dp.upload(u, nc * 2, ny * 2)) || (r = dp.upload(v, nc * 2, (ny + nc) * 2)) ||
+        (r = kat_run(launch_planes_to_fmt(p, (int)w, (int)w, (int)h, fmt, pitch, df.as<uint8_t>(), col, nullptr),
+                     "k_planes_to_fmt")) ||
+        (r = df.download(frame, bytes)))
+      return r;
   }
-done:
-  (void)hipFree(df);
-  (void)hipFree(dp);
-  return r;
+  return kSuccess;
 }
 
 }  // extern "C"

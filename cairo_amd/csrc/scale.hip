@@ -23,25 +23,29 @@
 // its address is 4-byte aligned and it lies inside the row, else byte loads
 // of the bytes inside the row: nothing outside the source's rows is read, and
 // nothing outside the tight output frame is written.  No LDS, no scratch.
+// The output dword goes through strip_access.h's store_bytes<4>; the status
+// values, fail() and the KAT's device buffers are hip_status.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdio>
+#include <memory>
 
 #include "../../include/cairo_amd.h"
+#include "hip_status.h"
 #include "scale.h"
+#include "strip_access.h"
 
 namespace cairo {
 
 namespace {
 
 constexpr int kScaleThreads = 128;  // a workgroup spans 512 output bytes of one plane row
-constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
 // Sizes are bounded so that o * L and s * P (at most lcm(S, D)) stay in 31 bits.
 constexpr uint32_t kMaxSourceSide = 32768;
 
 // Bytes j4 .. j4 + 3 of a row of `bytes` bytes as a little-endian dword; bytes
-// outside the row read as 0 and are not touched.
+// outside the row read as 0 and are not touched.  (Not strip_access.h's
+// load_bytes: a column can be cut at the row's start as well as at its end.)
 __device__ __forceinline__ uint32_t load_column(const uint8_t* row, int j4, int bytes) {
   const uint8_t* p = row + j4;
   if (j4 >= 0 && j4 + 4 <= bytes && ((uintptr_t)p & 3) == 0) return *(const uint32_t*)p;
@@ -119,7 +123,7 @@ __device__ __forceinline__ void scale_strip(const Plane& p, const ScaleFrame& f,
   // (acc + (N >> 1)) / N, N = lx * ly: the host's floor(2^32 / N) gives the
   // quotient or one less (the numerator is below 2^31)
   const uint32_t nn = f.lx * f.ly;
-  uint32_t out = 0;
+  uint32_t out[1] = {0};
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const uint32_t num = acc[k] + (nn >> 1);
@@ -127,16 +131,9 @@ __device__ __forceinline__ void scale_strip(const Plane& p, const ScaleFrame& f,
     uint32_t r = num - q * nn;
     if (r >= nn) q++, r -= nn;
     if (r >= nn) q++;
-    out |= (q & 255u) << (8 * k);
+    out[0] |= (q & 255u) << (8 * k);
   }
-  uint8_t* d = p.dst + (size_t)p.row * p.dpitch + b0;
-  if (n == 4 && ((uintptr_t)d & 3) == 0) {
-    *(uint32_t*)d = out;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (k < n) d[k] = (uint8_t)(out >> (8 * k));
-  }
+  store_bytes<4>(p.dst + (size_t)p.row * p.dpitch + b0, n, out);
 }
 
 // grid: x strips of a row, y rows of the frame's planes one after the other
@@ -179,12 +176,6 @@ __global__ __launch_bounds__(kScaleThreads) void k_scale_batch(ScaleArgs a) {
   p.dst = dchroma + (v ? (size_t)(dw >> 1) * (dh >> 1) : 0);
   p.sbytes = (int)f.sw >> 1, p.dbytes = dw >> 1, p.row = row - (v ? dh / 2 : 0);
   scale_strip<1>(p, f, strip);
-}
-
-int fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return kSuccess;
-  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
-  return kHardwareFail;
 }
 
 uint32_t gcd32(uint32_t a, uint32_t b) {
@@ -263,23 +254,17 @@ int cairo_kat_scale(int fmt, uint32_t pitch, const cairo_source* src, const uint
     return kInvalidArg;
   int r = fail(hipSetDevice(device), "hipSetDevice");
   if (r) return r;
-  uint8_t *ds = nullptr, *dd = nullptr;
-  ScaleArgs* a = new ScaleArgs();
-  a->dw = (int)dst_w, a->dh = (int)dst_h, a->nframes = 1;
   const size_t mis = (uintptr_t)frame & 3;  // the device copy keeps the source's address modulo 4
   dbytes += CAIRO_KAT_SCALE_GUARD;
-  if ((r = fail(hipMalloc(&ds, sbytes + mis), "malloc")) || (r = fail(hipMalloc(&dd, dbytes), "malloc"))) goto done;
-  (void)scale_plan(fmt, pitch, src, dst_w, dst_h, ds + mis, dd, &a->f[0]);
-  if ((r = fail(hipMemcpy(ds + mis, frame, sbytes, hipMemcpyHostToDevice), "h2d")) ||
-      (r = fail(hipMemcpy(dd, out, dbytes, hipMemcpyHostToDevice), "h2d")) ||
-      (r = fail(launch_scale_batch(*a, nullptr), "k_scale_batch")) || (r = fail(hipDeviceSynchronize(), "sync")) ||
-      (r = fail(hipMemcpy(out, dd, dbytes, hipMemcpyDeviceToHost), "d2h")))
-    goto done;
-done:
-  delete a;
-  (void)hipFree(ds);
-  (void)hipFree(dd);
-  return r;
+  KatBuffer ds, dd;
+  if ((r = ds.alloc(sbytes, mis)) || (r = dd.alloc(dbytes))) return r;
+  std::unique_ptr<ScaleArgs> a(new ScaleArgs());
+  a->dw = (int)dst_w, a->dh = (int)dst_h, a->nframes = 1;
+  (void)scale_plan(fmt, pitch, src, dst_w, dst_h, ds.as<uint8_t>(), dd.as<uint8_t>(), &a->f[0]);
+  if ((r = ds.upload(frame, sbytes)) || (r = dd.upload(out, dbytes)) ||
+      (r = kat_run(launch_scale_batch(*a, nullptr), "k_scale_batch")) || (r = dd.download(out, dbytes)))
+    return r;
+  return kSuccess;
 }
 
 }  // extern "C"

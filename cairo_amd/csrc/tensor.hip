@@ -19,15 +19,17 @@
 // and its address is a multiple of 4, else byte accesses.  Nothing outside the
 // W x H elements of the three channels is read or written on the tensor side,
 // nothing outside the tight frame on the RGB24 side.  No LDS, no scratch.
+// The status values, fail() and the KAT's device buffers are hip_status.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
+#include <memory>
 #include <utility>
 
 #include "../../include/cairo_amd.h"
+#include "hip_status.h"
 #include "tensor.h"
 #include "tensor_pixel.h"
 
@@ -36,7 +38,6 @@ namespace cairo {
 namespace {
 
 constexpr int kTensorThreads = 128;  // a workgroup spans 512 pixels of one row
-constexpr int kSuccess = 0, kInvalidArg = 1, kHardwareFail = 5;  // evx_status (base.h:150-172)
 constexpr uint64_t kMaxSpanElems = 1ull << 40;
 
 template <uint32_t DT>
@@ -45,6 +46,8 @@ struct ElemSize {
 };
 
 // The element bits of columns 0..n-1 of a strip (zero beyond n).  p: column 0;
+// (Not strip_access.h's accessors: the elements are 1, 2 or 4 bytes wide and a
+// column step apart, and the wide access is 4, 8 or 16 bytes accordingly.)
 // step: bytes from one column to the next; vec: the 4 elements are contiguous,
 // all inside the row, and p is aligned to the 4-element access.
 template <uint32_t DT>
@@ -105,7 +108,8 @@ __device__ __forceinline__ void store_elems(uint8_t* p, int64_t step, bool vec, 
 struct Strip {
   int y, px0, n;
   uint8_t* rgb;  // the strip's first RGB24 byte
-  bool rgb_vec;  // whole and dword-aligned: three dword accesses
+  bool rgb_vec;  // whole and dword-aligned: three dword accesses (decided once per strip, for both
+                 // directions, so not strip_access.h's load_bytes / store_bytes, which decide per access)
 };
 
 __device__ __forceinline__ bool make_strip(const TensorArgs& a, const TensorFrame& f, Strip* s) {
@@ -221,12 +225,6 @@ __global__ __launch_bounds__(kTensorThreads) void k_tensor_unpack(TensorArgs a) 
   }
 }
 
-int fail(hipError_t e, const char* what) {
-  if (e == hipSuccess) return kSuccess;
-  fprintf(stderr, "[cairo_amd] %s: %s\n", what, hipGetErrorString(e));
-  return kHardwareFail;
-}
-
 bool launch_ok(const TensorArgs& a) {
   return a.nframes >= 1 && a.nframes <= kTensorFrames && a.w >= 1 && a.h >= 1 && a.h <= 65535;
 }
@@ -299,24 +297,17 @@ int cairo_kat_tensor(int dir, const cairo_tensor* desc, uint32_t w, uint32_t h, 
   int r = fail(hipSetDevice(device), "hipSetDevice");
   if (r) return r;
   const size_t rbytes = (size_t)w * h * 3 + CAIRO_KAT_TENSOR_GUARD;
-  const size_t mis = (uintptr_t)tensor & 15;  // the device copy keeps the tensor's address modulo 16
-  uint8_t *dt = nullptr, *dr = nullptr;
-  TensorArgs* a = new TensorArgs();
+  const size_t mis = (uintptr_t)tensor & 15;  // the device copy keeps the tensor's address modulo 16 (tensor_bytes + 16 allocated)
+  KatBuffer dt, dr;
+  if ((r = dt.alloc(tensor_bytes + 16 - mis, mis)) || (r = dr.alloc(rbytes))) return r;
+  std::unique_ptr<TensorArgs> a(new TensorArgs());
   a->w = (int)w, a->h = (int)h, a->nframes = 1;
-  if ((r = fail(hipMalloc(&dt, tensor_bytes + 16), "malloc")) || (r = fail(hipMalloc(&dr, rbytes), "malloc"))) goto done;
-  a->f[0].tensor = dt + mis, a->f[0].rgb = dr, a->f[0].d = *desc;
-  if ((r = fail(hipMemcpy(dt + mis, tensor, tensor_bytes, hipMemcpyHostToDevice), "h2d")) ||
-      (r = fail(hipMemcpy(dr, rgb24, rbytes, hipMemcpyHostToDevice), "h2d")) ||
-      (r = fail(dir ? launch_tensor_unpack(*a, nullptr) : launch_tensor_pack_batch(*a, nullptr), "k_tensor")) ||
-      (r = fail(hipDeviceSynchronize(), "sync")) ||
-      (r = fail(hipMemcpy(tensor, dt + mis, tensor_bytes, hipMemcpyDeviceToHost), "d2h")) ||
-      (r = fail(hipMemcpy(rgb24, dr, rbytes, hipMemcpyDeviceToHost), "d2h")))
-    goto done;
-done:
-  delete a;
-  (void)hipFree(dt);
-  (void)hipFree(dr);
-  return r;
+  a->f[0].tensor = dt.as<uint8_t>(), a->f[0].rgb = dr.as<uint8_t>(), a->f[0].d = *desc;
+  if ((r = dt.upload(tensor, tensor_bytes)) || (r = dr.upload(rgb24, rbytes)) ||
+      (r = kat_run(dir ? launch_tensor_unpack(*a, nullptr) : launch_tensor_pack_batch(*a, nullptr), "k_tensor")) ||
+      (r = dt.download(tensor, tensor_bytes)) || (r = dr.download(rgb24, rbytes)))
+    return r;
+  return kSuccess;
 }
 
 }  // extern "C"

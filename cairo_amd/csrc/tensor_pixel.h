@@ -2,7 +2,8 @@
 // (include/cairo_amd.h, cairo_tensor), as __host__ __device__
 // functions: the kernels of tensor.hip, cairo_tensor_host and the stand-alone
 // sanitizer program (tests/sanitize/tensor_host_main.cpp) all compile this one
-// text.  It needs nothing but <math.h>, <stdint.h> and <string.h>.
+// text.  It needs nothing but <math.h>, <stdint.h>, <string.h> and
+// pixel_common.h (the host + device macro and the register pin, pin8).
 //
 // Everything is IEEE binary32 with one stated rounding per step: the element
 // to float conversions are exact, fmaf rounds once, rintf rounds to nearest
@@ -15,11 +16,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define CAIRO_HD __host__ __device__ __forceinline__
-#else
-#define CAIRO_HD inline
-#endif
+#include "pixel_common.h"
 
 namespace cairo {
 
@@ -76,18 +73,12 @@ CAIRO_HD uint32_t f32_to_bf16_bits(float f) {
 
 // Steps 2 and 3 of the input map, and the U8 store of the output map:
 // NaN -> 0, else rintf (nearest even), clamped to 0..255; infinities clamp.
-// Like sat8 of pixfmt.hip, the sample is pinned to a register of its own
-// before anything packs it (a clamp fused with byte packing into
-// v_ashr_pk_u8_i32 corrupted bytes 2 and 3).
+// The sample is pinned before anything packs it (pin8).
 CAIRO_HD uint32_t tensor_sat8(float t) {
   if (t != t) return 0u;
   float r = rintf(t);
   r = r < 0.f ? 0.f : (r > 255.f ? 255.f : r);
-  uint32_t s = (uint32_t)(int)r;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(s));
-#endif
-  return s;
+  return pin8((uint32_t)(int)r);
 }
 
 // Element bits (zero-extended, as stored) -> step 1's float.

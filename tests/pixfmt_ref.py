@@ -76,8 +76,20 @@ def planes_to_frame(y, u, v, fmt: int, w: int, h: int, pitch: int = 0, fill: int
 
 
 def frame_to_planes(buf: np.ndarray, fmt: int, w: int, h: int, pitch: int = 0):
-    """An I420 / NV12 frame as tight internal planes: Y8 + 16, U8, V8."""
+    """A frame as tight internal planes.  I420 / NV12: Y8 + 16, U8, V8.
+    RGB24 / BGR24: the codec's own rule (cairo_amd/csrc/rgb_pixel.h restated):
+    a luma sample per pixel, a chroma sample the rounded mean of the four
+    chroma terms of a 2 x 2 quad, `/ 256` truncating towards zero."""
     vw = views(buf, fmt, w, h, pitch)
+    if fmt in (RGB24, BGR24):
+        px = vw[0].astype(np.int32)
+        r, g, b = (px[..., 0], px[..., 1], px[..., 2]) if fmt == RGB24 else (px[..., 2], px[..., 1], px[..., 0])
+        trunc256 = lambda x: np.where(x < 0, -((-x) // 256), x // 256)  # noqa: E731
+        quad = lambda t: (t.reshape(h // 2, 2, w // 2, 2).sum(axis=(1, 3)) + 2) >> 2  # noqa: E731
+        y = ((77 * r + 150 * g + 29 * b + 128) >> 8) + 16
+        u = quad(trunc256(-43 * r - 85 * g + 128 * b + 128) + 128)
+        v = quad(trunc256(128 * r - 107 * g - 21 * b + 128) + 128)
+        return y.astype(np.int16), u.astype(np.int16), v.astype(np.int16)
     y = vw[0].astype(np.int16) + 16
     if fmt == I420:
         return y, vw[1].astype(np.int16), vw[2].astype(np.int16)

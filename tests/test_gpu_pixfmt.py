@@ -125,6 +125,42 @@ def test_kat_input(orc, cairo, fmt, size):
             np.testing.assert_array_equal(frame, before, err_msg=f"{tag}: the source frame")
 
 
+def test_default_rgb24_path_equals_its_restatements(orc, cairo):
+    """The default input path (tight RGB24 through Context.submit: k_convert_batch)
+    on bytes the encoder tests never feed it, against both restatements of its
+    rule: tests/pixfmt_ref.py (and, through it, the oracle's convert) and the
+    strip kernel (cairo_kat_convert, RGB24).  70x34: chroma width 35, wa != w,
+    nothing a multiple of 4.  1030x18: 515 quad columns, so a row spans three of
+    k_convert_batch's 256-thread workgroups and the last holds three threads;
+    wa = 1040."""
+    corners = ((0, 0, 0), (255, 255, 255), (255, 0, 0), (0, 0, 255))
+    n = 0
+    for w, h in ((70, 34), (1030, 18)):
+        rng = np.random.default_rng(3000 + w)
+        ctx = cairo.Context(w, h, 4, stages=8)
+        try:
+            for t in range(2):  # two intra frames
+                rgb = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+                rgb[0, 0] = rgb[h - 1, w - 1] = corners[n % 4]
+                n += 1
+                frame = ref.rgb_to_frame(rgb, ref.RGB24)
+                ctx.encode_frame(rgb, t, False, 16)  # Context.submit with its defaults, wait, release
+                got = [p[:ph, :pw] for p, (ph, pw) in
+                       zip(ctx.read_planes(0), ((h, w), (h // 2, w // 2), (h // 2, w // 2)))]
+                want = ref.frame_to_planes(frame, ref.RGB24, w, h)
+                for a, b in zip(want, _tight_convert(orc, rgb)):
+                    np.testing.assert_array_equal(a, b, err_msg="the numpy restatement against the oracle")
+                strip = (np.full((h, w), -1, np.int16), np.full((h // 2, w // 2), -1, np.int16),
+                         np.full((h // 2, w // 2), -1, np.int16))
+                _kat(cairo, 0, ref.RGB24, w, h, 0, frame, *strip)
+                for g, wn, s, name in zip(got, want, strip, "YUV"):
+                    tag = f"{w}x{h} frame {t} {name}"
+                    np.testing.assert_array_equal(g, wn, err_msg=f"{tag}: k_convert_batch against pixfmt_ref")
+                    np.testing.assert_array_equal(g, s, err_msg=f"{tag}: k_convert_batch against the strip kernel")
+        finally:
+            ctx.close()
+
+
 # ---------------------------------------------------------------------------
 # KAT, output side
 # ---------------------------------------------------------------------------

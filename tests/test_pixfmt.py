@@ -116,6 +116,23 @@ def test_reference_round_trip_and_mask():
     assert (yy[0, 0], yy[0, 1], uu[0, 0], vv[0, 0]) == (16, 271, 0, 255)
 
 
+def test_reference_rgb_rule_equals_oracle(orc):
+    """frame_to_planes on RGB24 / BGR24 frames restates the codec's RGB -> YUV
+    rule: random bytes, and the pure colours whose chroma terms reach 256 and 1,
+    must give the oracle's convert, tight or pitched."""
+    rng = np.random.default_rng(11)
+    w, h = 70, 34
+    rgb = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    rgb[0:2, 0:2], rgb[0:2, 2:4], rgb[2:4, 0:2], rgb[2:4, 2:4] = (0, 0, 255), (255, 0, 0), (0, 255, 0), (255, 255, 255)
+    want = ref.oracle_input_planes(orc, rgb)
+    assert want[1].max() == 256 and want[2].max() == 256
+    for fmt, pitch in ((ref.RGB24, 0), (ref.RGB24, 3 * w + 1), (ref.BGR24, 0)):
+        got = ref.frame_to_planes(ref.rgb_to_frame(rgb, fmt, pitch, fill=0xFF), fmt, w, h, pitch)
+        for a, b, name in zip(got, want, "yuv"):
+            assert a.dtype == np.int16
+            np.testing.assert_array_equal(a, b[:a.shape[0], :a.shape[1]], err_msg=f"{ref.FMT_NAMES[fmt]} {name}")
+
+
 def test_gpu_inputs_fit_8_bits(orc):
     """Every frame the GPU tests submit as I420 / NV12: the oracle's planes(0)
     must come back unchanged from planes -> frame -> planes inside w x h (the
