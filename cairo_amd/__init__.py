@@ -122,6 +122,10 @@ def lib() -> ctypes.CDLL:
         "cairo_kat_tensor": (I, [I, P, U, U, P, ctypes.c_uint64, P, I]),
         "cairo_ctx_submit_tensor": (I, [P, P, P, U, U, U, ctypes.POINTER(I)]),
         "cairo_stream_submit_tensor": (I, [P, P, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_tensor_scale_check": (I, [P, P, P, U, U, ctypes.POINTER(ctypes.c_uint64)]),
+        "cairo_ctx_submit_tensor_scaled": (I, [P, P, P, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_stream_submit_tensor_scaled": (I, [P, P, P, P, U, U, U, ctypes.POINTER(I)]),
+        "cairo_kat_tensor_scale": (I, [P, P, P, ctypes.c_uint64, U, U, P, I]),
         "cairo_ctx_decode_frame_tensor": (I, [P, P, P, U, P, P]),
         "cairo_ctx_fetch_recon_tensor": (I, [P, I, P, P]),
         "evx_encoder_set_input_tensor": (I, [P, P]),
@@ -547,6 +551,57 @@ def kat_tensor(direction: int, desc: TensorDesc, w: int, h: int, nbytes: int, rg
         "cairo_kat_tensor")
 
 
+def _tensor_source(d: TensorDesc, src_size, crop) -> "_Source":
+    """The cairo_source of a scaled tensor submit: the source size is the
+    tensor's own (W, H) where its shape gave one, else src_size."""
+    own = (d.width, d.height) if d.width is not None else None
+    if src_size is None:
+        if own is None:
+            raise ValueError("a tensor given as (ptr, dtype, strides) or as a shapeless TensorDesc is scaled with "
+                             "src_size = (w, h)")
+        src_size = own
+    s = _source(src_size, crop)
+    if own is not None and (s.width, s.height) != own:
+        raise ValueError(f"src_size {tuple(src_size)} contradicts the tensor's shape, a {own[0]}x{own[1]} frame")
+    return s
+
+
+def tensor_scale_check(desc: TensorDesc, src_size, dst_w: int, dst_h: int, crop=None, ptr: int | None = None):
+    """-> the span in bytes of the source tensor of a scaled tensor submit, or
+    None when it is refused (cairo_tensor_scale_check): desc must be valid for
+    a frame of src_size = (w, h) (tensor_check), and that size, or its region
+    crop = (x, y, w, h), must scale to dst_w x dst_h as an RGB24 frame does
+    (scale_check).  src_size None: the size desc got from a shape.  ptr: another
+    base address, of which only the alignment counts.  No device needed."""
+    if not all(isinstance(x, (int, np.integer)) and 0 <= x < 2 ** 32 for x in (dst_w, dst_h)):
+        return None
+    try:
+        s = _tensor_source(desc, src_size, crop)
+    except (ValueError, TypeError):
+        return None
+    span = ctypes.c_uint64()
+    base = desc.ptr if ptr is None else ptr
+    if lib().cairo_tensor_scale_check(ctypes.byref(desc.c), base, ctypes.byref(s), int(dst_w), int(dst_h),
+                                      ctypes.byref(span)):
+        return None
+    return span.value
+
+
+def kat_tensor_scale(desc: TensorDesc, src_size, nbytes: int, dst_w: int, dst_h: int, rgb: np.ndarray, crop=None,
+                     device: int = 0) -> None:
+    """The scaled tensor submit's kernel on host buffers, without a context
+    (cairo_kat_tensor_scale), with kat_tensor's conventions: the nbytes of
+    host memory at desc.ptr (a tensor of src_size, and any guard) and rgb
+    (3 * dst_w * dst_h + KAT_TENSOR_GUARD uint8) are uploaded, the kernel
+    runs, and both are read back in place."""
+    if not isinstance(rgb, np.ndarray) or rgb.dtype != np.uint8 or rgb.size != 3 * dst_w * dst_h + KAT_TENSOR_GUARD or \
+            not rgb.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"rgb must be a C-contiguous uint8 array of {3 * dst_w * dst_h + KAT_TENSOR_GUARD} bytes")
+    s = _tensor_source(desc, src_size, crop)
+    _ck(lib().cairo_kat_tensor_scale(ctypes.byref(desc.c), ctypes.byref(s), desc.ptr, nbytes, dst_w, dst_h, _ptr(rgb),
+                                     device), "cairo_kat_tensor_scale")
+
+
 def _frame_tensor(t, width: int, height: int, output: bool, kw: dict) -> TensorDesc:
     """The descriptor of a tensor handed to a context of width x height."""
     d = tensor_desc(t, output=output, **kw)
@@ -685,14 +740,26 @@ def _submit(prefix: str, handle, width: int, height: int, keep: dict, rgb, index
 
 
 def _submit_tensor(prefix: str, handle, width: int, height: int, keep: dict, t, index: int, inter: bool, quality: int,
-                   sync: bool, desc: dict) -> int:
-    """Context.submit_tensor and Stream.submit_tensor, as _submit."""
-    d = _frame_tensor(t, width, height, False, desc)
-    if sync:
-        _sync_producer(d.owner)
+                   sync: bool, desc: dict, scaled: bool = False, crop=None, src_size=None) -> int:
+    """Context.submit_tensor and Stream.submit_tensor, as _submit.  scaled or
+    a crop: the tensor is the source of a scaled tensor submit."""
     tk = ctypes.c_int()
-    _ck(getattr(lib(), prefix + "_submit_tensor")(handle, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
-                                                  ctypes.byref(tk)), prefix + "_submit_tensor")
+    if scaled or crop is not None:
+        d = tensor_desc(t, output=False, **desc)
+        s = _tensor_source(d, src_size, crop)
+        if sync:
+            _sync_producer(d.owner)
+        _ck(getattr(lib(), prefix + "_submit_tensor_scaled")(handle, d.ptr, ctypes.byref(d.c), ctypes.byref(s), index,
+                                                             int(inter), quality, ctypes.byref(tk)),
+            prefix + "_submit_tensor_scaled")
+    else:
+        if src_size is not None:
+            raise ValueError("src_size belongs to a scaled tensor submit: pass scaled=True or a crop")
+        d = _frame_tensor(t, width, height, False, desc)
+        if sync:
+            _sync_producer(d.owner)
+        _ck(getattr(lib(), prefix + "_submit_tensor")(handle, d.ptr, ctypes.byref(d.c), index, int(inter), quality,
+                                                      ctypes.byref(tk)), prefix + "_submit_tensor")
     keep[tk.value] = d
     return tk.value
 
@@ -736,16 +803,24 @@ class Context:
         return _submit("cairo_ctx", self.h, self.width, self.height, self._keep, rgb, index, inter, quality, on_device,
                        fmt, pitch, src_size, crop)
 
-    def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, **desc) -> int:
+    def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, scaled: bool = False,
+                      crop=None, src_size=None, **desc) -> int:
         """Submit a tensor frame in device memory (cairo_ctx_submit_tensor): t
         and the keywords mul, add, value_range are tensor_desc's (or t is a
         TensorDesc).  Produces the bits of submitting the RGB24 frame the input
         map gives.  t is kept alive until the ticket's wait and must not
         change before it.  sync: synchronise the producer's current stream
         first when torch is already imported (the C ABI leaves that ordering to
-        the caller)."""
+        the caller).
+
+        scaled=True or crop = (x, y, w, h): t is a larger tensor, which (or
+        whose region) is mapped to samples and scaled to the context's size on
+        the GPU in one pass (cairo_ctx_submit_tensor_scaled, see
+        tensor_scale_check): the bits of Context.submit(..., src_size=...) of
+        the packed RGB24 frame.  The source size is t's own; src_size = (w, h)
+        gives it for a (ptr, dtype, strides) or a shapeless TensorDesc."""
         return _submit_tensor("cairo_ctx", self.h, self.width, self.height, self._keep, t, index, inter, quality, sync,
-                              desc)
+                              desc, scaled, crop, src_size)
 
     def wait(self, ticket: int, copy: bool = True) -> FrameOutputs:
         r = _FrameResult()
@@ -1236,11 +1311,13 @@ class Stream:
         return _submit("cairo_stream", self.h, self.ctx.width, self.ctx.height, self._keep, rgb, index, inter, quality,
                        on_device, fmt, pitch, src_size, crop)
 
-    def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, **desc) -> int:
-        """A tensor frame, as Context.submit_tensor (cairo_stream_submit_tensor);
-        t is kept alive until the frame is collected."""
+    def submit_tensor(self, t, index: int, inter: bool, quality: int, sync: bool = True, scaled: bool = False,
+                      crop=None, src_size=None, **desc) -> int:
+        """A tensor frame, as Context.submit_tensor (cairo_stream_submit_tensor;
+        scaled / crop / src_size: cairo_stream_submit_tensor_scaled); t is kept
+        alive until the frame is collected."""
         return _submit_tensor("cairo_stream", self.h, self.ctx.width, self.ctx.height, self._keep, t, index, inter,
-                              quality, sync, desc)
+                              quality, sync, desc, scaled, crop, src_size)
 
     def collect(self, ticket: int, out: np.ndarray | None = None, pos: int = 0):
         """Append the frame's payload at bit pos of out -> new pos; with out

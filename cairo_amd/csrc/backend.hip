@@ -225,7 +225,9 @@ struct cairo_ctx {
     // (cairo_ctx_submit_scaled), kTensor (cairo_ctx_submit_tensor, DESIGN
     // §4.15): f.rgb is the staging slot, tight, which the launch's k_scale_batch
     // / k_tensor_pack_batch fills from `scale` / `tens` before the convert.
-    enum Kind : uint8_t { kStaged, kDevice, kScaled, kTensor };
+    // kTensorScaled (cairo_ctx_submit_tensor_scaled): the same,
+    // filled by k_tensor_scale_batch from `tscale`.
+    enum Kind : uint8_t { kStaged, kDevice, kScaled, kTensor, kTensorScaled };
     FrameDesc f;
     Kind kind;
     // Layout as the convert kernel reads it (CAIRO_FMT_*, row pitch in bytes):
@@ -237,6 +239,7 @@ struct cairo_ctx {
     union {
       ScaleFrame scale;
       TensorFrame tens;
+      TensorScaleFrame tscale;
     };
   };
   Pending pend[kMaxBatch];
@@ -701,7 +704,8 @@ int enqueue_uploads(cairo_ctx* c, Launch& l) {
 }
 
 // Inputs: the pre-pass of one kind of frame (scaled: k_scale_batch, tensor:
-// k_tensor_pack_batch) fills those frames' staging slots before the convert
+// k_tensor_pack_batch, scaled tensor: k_tensor_scale_batch) fills those
+// frames' staging slots before the convert
 // reads them: one kernel, and another whenever its argument block is full.
 // A launch without such a frame enqueues nothing here.  A slot's previous
 // frame may have been converted on the other launch stream (a ticket may be
@@ -709,7 +713,7 @@ int enqueue_uploads(cairo_ctx* c, Launch& l) {
 template <class Args, class Frame>
 int enqueue_prepass(cairo_ctx* c, const Launch& l, Pending::Kind kind, Frame Pending::*frame,
                     hipError_t (*launch)(const Args&, hipStream_t)) {
-  Args a;  // only the header is written here: both blocks are {frame width, height, nframes, reserved, f[]}
+  Args a;  // only the header is written here: every block is {frame width, height, nframes, reserved, f[]}
   auto& [aw, ah, an, ares, af] = a;
   aw = (int)c->w, ah = (int)c->h, an = 0, ares = 0;
   constexpr int cap = (int)(sizeof(af) / sizeof(af[0]));
@@ -924,6 +928,7 @@ int flush(cairo_ctx* c) {
   if (!r) r = enqueue_uploads(c, l);
   if (!r) r = enqueue_prepass(c, l, Pending::kScaled, &Pending::scale, launch_scale_batch);
   if (!r) r = enqueue_prepass(c, l, Pending::kTensor, &Pending::tens, launch_tensor_pack_batch);
+  if (!r) r = enqueue_prepass(c, l, Pending::kTensorScaled, &Pending::tscale, launch_tensor_scale_batch);
   if (!r) r = enqueue_convert(c, l);
   // engine and batch wait
   if (!r) r = enqueue_engine(c, l);
@@ -1367,6 +1372,12 @@ int cairo_ctx_submit_tensor(cairo_ctx* c, const void* base, const cairo_tensor* 
   if (!desc) return kInvalidArg;
   return submit_frame(c, {(const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, nullptr, desc}, index, type, quality,
                       ticket);
+}
+
+int cairo_ctx_submit_tensor_scaled(cairo_ctx* c, const void* base, const cairo_tensor* desc, const cairo_source* src,
+                                   uint32_t index, uint32_t type, uint32_t quality, int* ticket) {
+  if (!desc || !src) return kInvalidArg;
+  return submit_frame(c, {(const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, src, desc}, index, type, quality, ticket);
 }
 
 static const char* timeout_kind_name(int k) {
@@ -2052,18 +2063,26 @@ namespace cairo {
 // (src.base: a device frame of the source's size and pitch) and a tensor frame
 // (src.base: element (0, 0, 0) of a device tensor) are recorded as frames whose
 // f.rgb is their staging slot, tight, which the launch's pre-pass fills from
-// the source (flush: k_scale_batch, k_tensor_pack_batch).
+// the source (flush: k_scale_batch, k_tensor_pack_batch); a source that is both
+// (a tensor of the source's size) by k_tensor_scale_batch.
 int submit_frame(cairo_ctx* c, const FrameSource& src, uint32_t index, uint32_t type, uint32_t quality,
                  int* ticket) {
   const uint8_t* rgb = src.base;
   if (!c || !rgb || !ticket || quality < 1 || quality > 31 || type > 1) return kInvalidArg;
-  const Pending::Kind kind = src.tensor ? Pending::kTensor : src.scaled ? Pending::kScaled
+  const Pending::Kind kind = src.tensor ? (src.scaled ? Pending::kTensorScaled : Pending::kTensor)
+                             : src.scaled ? Pending::kScaled
                              : src.on_device ? Pending::kDevice : Pending::kStaged;
-  const char* who = src.tensor ? "submit_tensor" : src.scaled ? "submit_scaled" : "submit";
+  const char* who = src.tensor ? (src.scaled ? "submit_tensor_scaled" : "submit_tensor")
+                    : src.scaled ? "submit_scaled" : "submit";
   uint64_t frame_bytes = 0;  // of the source as it lies in memory (a tensor's span)
   uint32_t tight = 3 * c->w;
   ScaleFrame plan{};
-  if (kind == Pending::kTensor) {
+  TensorScaleFrame tplan{};
+  if (kind == Pending::kTensorScaled) {
+    // the tensor has the source's size; the slot gets the tight RGB24 frame of the context's
+    if (tensor_scale_plan(src.tensor, rgb, src.scaled, c->w, c->h, nullptr, &frame_bytes, &tplan) != kSuccess)
+      return kInvalidArg;
+  } else if (kind == Pending::kTensor) {
     if (tensor_check(src.tensor, rgb, c->w, c->h, &frame_bytes) != kSuccess) return kInvalidArg;
   } else if (kind == Pending::kScaled) {
     // (the scaler's grid has a row per plane row: at most 65535)
@@ -2103,6 +2122,9 @@ int submit_frame(cairo_ctx* c, const FrameSource& src, uint32_t index, uint32_t 
   if (kind == Pending::kScaled) {
     plan.dst = slot_rgb(c, slot);
     p.scale = plan;
+  } else if (kind == Pending::kTensorScaled) {
+    tplan.rgb = slot_rgb(c, slot);
+    p.tscale = tplan;
   } else if (kind == Pending::kTensor) {
     p.tens = TensorFrame{const_cast<uint8_t*>(rgb), slot_rgb(c, slot), *src.tensor};
   } else if (kind == Pending::kStaged) {

@@ -300,6 +300,14 @@ int cairo_stream_submit_tensor(cairo_stream* s, const void* base, const cairo_te
                        ticket);
 }
 
+int cairo_stream_submit_tensor_scaled(cairo_stream* s, const void* base, const cairo_tensor* desc,
+                                      const cairo_source* src, uint32_t index, uint32_t type, uint32_t quality,
+                                      int* ticket) {
+  if (!desc || !src) return kInvalidArg;
+  return stream_submit(s, {(const uint8_t*)base, 1, CAIRO_FMT_RGB24, 0, true, src, desc}, index, type, quality,
+                       ticket);
+}
+
 int cairo_stream_collect(cairo_stream* s, int ticket, uint8_t* out, uint64_t out_bytes,
                          uint64_t* bit_pos) {
   if (!s || ticket < 0 || !bit_pos) return kInvalidArg;

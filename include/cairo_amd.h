@@ -67,7 +67,10 @@ extern "C" {
  *      only: the enumerators CAIRO_FMT_YUY2, CAIRO_FMT_UYVY and CAIRO_FMT_P010
  *      (8, 9, 10; values the entry points above refused before) and
  *      cairo_frame_fold.  Every call that took a format value takes them,
- *      except the scaled submit.  Nothing existing changes. */
+ *      except the scaled submit.  Nothing existing changes.
+ *   4  (unchanged) the scaled tensor submit adds entry points only:
+ *      cairo_tensor_scale_check, cairo_ctx_submit_tensor_scaled,
+ *      cairo_stream_submit_tensor_scaled, cairo_kat_tensor_scale. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -424,6 +427,61 @@ CAIRO_API int cairo_kat_tensor(int dir, const cairo_tensor *desc, uint32_t w, ui
  * members. */
 CAIRO_API int cairo_ctx_submit_tensor(cairo_ctx *ctx, const void *base, const cairo_tensor *desc, uint32_t index,
                                       uint32_t type, uint32_t quality, int *ticket);
+
+/* ---- scaled tensor submit ----------------------------------
+ * One tensor in device memory -- a model's 4K output, a frame of a loader's
+ * batch -- feeds contexts of several sizes, with no packed full-size copy.  The
+ * tensor has src->width x src->height elements per channel and is described by
+ * a cairo_tensor exactly as for cairo_ctx_submit_tensor, with the source's
+ * width and height in place of the context's; src is the scaled submit's
+ * cairo_source (the source size and an optional even crop).
+ *
+ * Write pack for the input map of cairo_tensor (one fmaf, one rintf, a clamp,
+ * NaN -> 0) and scale for the area average of the scaled submit on a tight
+ * RGB24 frame.  The frame that is encoded is
+ *     scale(pack(tensor))   to the context's width x height:
+ * every source element is first mapped to its 8-bit sample, and the samples
+ * are then averaged in exact integers,
+ *     (sum wy wx s + ((Lx Ly) >> 1)) / (Lx Ly)                 (floor division)
+ * with no intermediate rounding.  So a scaled tensor submit produces exactly
+ * the bits of cairo_ctx_submit_scaled on the RGB24 frame pack(tensor), hence
+ * those of cairo_ctx_submit of the scaled frame: a ladder fed from a tensor
+ * gives the streams of a ladder fed from its packed copy.  (Rounding first,
+ * then averaging, composes two maps that are specified already and keeps the
+ * sum independent of its order; an average of floats would be neither.)
+ *
+ * Validity (EVX_ERROR_INVALID_ARGS; a refused submit takes no ticket):
+ * cairo_tensor_check(desc, base, src->width, src->height) holds, and so does
+ * every rule of cairo_scale_check(CAIRO_FMT_RGB24, 0, src, dst_w, dst_h): even
+ * sizes and crop values, the crop inside the source, D <= S <= 8 D per axis,
+ * 255 Lx Ly < 2^31, sides of at most 32768, reserved words 0.  The whole span
+ * of the source lies inside one device allocation of the context's GPU; a host
+ * pointer is refused.  Elements outside the crop are never read, the tensor is
+ * never written, and nothing but the slot's tight 3*W*H frame is written. */
+/* Validity of scaling the tensor (desc at address base, of which only the
+ * alignment is looked at) of src's size to dst_w x dst_h; *span_bytes (may be
+ * NULL) receives the span of the source tensor in bytes.  Host only, no device
+ * needed. */
+CAIRO_API int cairo_tensor_scale_check(const cairo_tensor *desc, const void *base, const cairo_source *src,
+                                       uint32_t dst_w, uint32_t dst_h, uint64_t *span_bytes);
+/* cairo_ctx_submit of the RGB24 frame scale(pack(tensor)) at the context's
+ * size.  base, its lifetime and its ordering are cairo_ctx_submit_tensor's; it
+ * is read when the frame's batch launches, by one pre-pass kernel per launch.
+ * A launch may mix scaled tensor frames of any dtype, strides, map, source
+ * size and crop with tensor, scaled and plain frames.  Allowed for group
+ * members.  The drop-in encoder does not take them. */
+CAIRO_API int cairo_ctx_submit_tensor_scaled(cairo_ctx *ctx, const void *base, const cairo_tensor *desc,
+                                             const cairo_source *src, uint32_t index, uint32_t type,
+                                             uint32_t quality, int *ticket);
+/* Known-answer check of the kernel on host buffers, without a context or the
+ * engine, with cairo_kat_tensor's conventions: tensor is tensor_bytes long
+ * from element (0,0,0) (at least the span); rgb24 holds the tight dst_w x
+ * dst_h frame followed by CAIRO_KAT_TENSOR_GUARD bytes.  Both are uploaded
+ * first and both are read back.  The device copy of tensor keeps tensor's
+ * address modulo 16. */
+CAIRO_API int cairo_kat_tensor_scale(const cairo_tensor *desc, const cairo_source *src, void *tensor,
+                                     uint64_t tensor_bytes, uint32_t dst_w, uint32_t dst_h, uint8_t *rgb24,
+                                     int device);
 
 /* Wait until the frame's block table and coefficients are host-visible. */
 CAIRO_API int cairo_ctx_wait(cairo_ctx *ctx, int ticket, cairo_frame_result *out);
@@ -795,6 +853,10 @@ CAIRO_API int cairo_stream_submit_scaled(cairo_stream *s, const uint8_t *frame, 
 /* cairo_stream_submit for a tensor frame (cairo_ctx_submit_tensor). */
 CAIRO_API int cairo_stream_submit_tensor(cairo_stream *s, const void *base, const cairo_tensor *desc, uint32_t index,
                                          uint32_t type, uint32_t quality, int *ticket);
+/* cairo_stream_submit for a scaled tensor frame (cairo_ctx_submit_tensor_scaled). */
+CAIRO_API int cairo_stream_submit_tensor_scaled(cairo_stream *s, const void *base, const cairo_tensor *desc,
+                                                const cairo_source *src, uint32_t index, uint32_t type,
+                                                uint32_t quality, int *ticket);
 /* Wait for the frame's payload and append it at bit *bit_pos of out
  * (out_bytes capacity, LSB-first; out == NULL only advances *bit_pos).  If it
  * does not fit, returns EVX_ERROR_CAPACITY_LIMIT (7) and keeps the payload:
