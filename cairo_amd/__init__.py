@@ -149,6 +149,7 @@ def lib() -> ctypes.CDLL:
         "cairo_ctx_set_debug": (I, [P, I]),
         "cairo_ctx_read_predeblock": (I, [P, P, P, P]),
         "cairo_ctx_read_stamps": (I, [P, P]),
+        "cairo_ctx_engine_variant": (I, [P]),
         "cairo_ctx_set_profiling": (I, [P, I]),
         "cairo_ctx_take_timings": (I, [P, P, ctypes.POINTER(I)]),
         "cairo_ctx_busy_intervals": (I, [P, P, I, ctypes.POINTER(I)]),
@@ -1051,6 +1052,11 @@ class Context:
         fr = out[: MAX_BATCH * fw].reshape(MAX_BATCH, fw)
         return (fr[:, :n_mb].reshape(MAX_BATCH, self.hmb, self.wmb, 12), fr[:, n_mb:].reshape(MAX_BATCH, self.hmb, 256),
                 out[MAX_BATCH * fw:MAX_BATCH * fw + 2], out[MAX_BATCH * fw + 2:].reshape(MAX_BATCH, self.hmb, ng, 12))
+
+    def engine_variant(self) -> int:
+        """The engine of the last launch enqueued: 0 plain, 1 general (diagnostics,
+        cross-device groups, decode)."""
+        return int(self.L.cairo_ctx_engine_variant(self.h))
 
     def set_profiling(self, enable: bool) -> None:
         _ck(self.L.cairo_ctx_set_profiling(self.h, int(enable)), "set_profiling")

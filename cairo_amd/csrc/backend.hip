@@ -153,6 +153,8 @@ struct cairo_ctx {
   const int32_t* prev_seg[2] = {};
   int32_t* prev_sync = nullptr;
   int prev_total = 0, prev_area = 0, prev_decode = 0;
+  bool prev_sys = false;   // some frame of the last launch had FrameDesc::sys
+  int engine_variant = 0;  // the last launch's engine: 0 plain, 1 general (cairo_ctx_engine_variant)
   int order_slope = kOrderSlope;  // of the task order tables (3N + 2 in an N-member group)
   long long batches = 0;             // launches so far
   // per-slot device buffers
@@ -642,6 +644,14 @@ int plan_launch(cairo_ctx* c, Launch& l) {
   e.ptotal = c->prev_decode == e.decode ? c->prev_total : 0;  // a worker runs one kind of task
   e.slope = c->order_slope;
   for (int i = 0; i < c->npend; i++) fh[i] = make_frame_view(e, c->pend[i].f, i);
+  // The plain engine (EngineArgs::general) has no diagnostics
+  // and only agent-scope hand-offs: for a launch without stamps, trace or
+  // inject none of whose frames -- its own, or those of the previous launch
+  // whose queues its workers serve -- is shared across devices.  A decode
+  // launch always takes the general engine.
+  bool sys = e.ptotal && c->prev_sys;
+  for (int i = 0; i < c->npend; i++) sys |= c->pend[i].f.sys != 0;
+  e.general = e.decode || e.stamps || e.trace || e.inject || sys;
   {  // half of the resident slots per launch, split between the pools
     const int total = 2 * (c->wg_rows > 0 ? std::min(c->wg_rows, (c->stamps ? 2 : 1) * c->max_rows) : c->max_rows);
     // default split: even, and 25/48 helpers (200 of 384) on large frames
@@ -804,6 +814,9 @@ int enqueue_engine(cairo_ctx* c, Launch& l) {
   c->prev_total = l.rows;
   c->prev_area = l.area;
   c->prev_decode = e.decode;
+  c->prev_sys = false;
+  for (int i = 0; i < e.nframes; i++) c->prev_sys |= l.fh[i].sys != 0;
+  c->engine_variant = e.general;
   if (tb) {
     CK(hipEventRecord(tb->ev[3], st));
     tb->frames = e.nframes;
@@ -2000,6 +2013,12 @@ int cairo_ctx_read_stamps(cairo_ctx* c, uint64_t* out) {
   if (r) return r;
   CK(hipMemcpy(out, c->stamps, stamp_words(c) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return kSuccess;
+}
+
+int cairo_ctx_engine_variant(cairo_ctx* c) {
+  if (!c) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return c->engine_variant;
 }
 
 int cairo_ctx_read_predeblock(cairo_ctx* c, int16_t* y, int16_t* u, int16_t* v) {

@@ -360,6 +360,12 @@ struct EngineArgs {
   int32_t* sync;           // SyncLayout words of this launch
   int32_t* sticky;         // TimeoutInfo words
   int inject;              // FrameArgs::inject
+  // Which engine launch_engine starts (host side only): 0 the
+  // plain instantiation -- no stamps, trace or inject in this launch, and no
+  // FrameDesc::sys among its frames or those of the previous launch whose
+  // queues it shares -- 1 the general one.  (In the padding before stamps:
+  // the kernel-argument offsets stay.)
+  int general;
   uint64_t* stamps;
   // Diagnostic time accounting of a build with CAIRO_ACCT=1 (nullptr = off):
   // [kAcctShards][kAcctWords] u64, 10 ns ticks summed per role and phase over

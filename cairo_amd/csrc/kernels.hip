@@ -142,10 +142,33 @@ __device__ __forceinline__ int wave_max(int v) {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// The engine's two instantiations, a compile-time mode M passed
+// down from k_engine.  The general one: every diagnostic (phase stamps, live
+// trace, the injected timeout) and the run-time choice of system scope for a
+// view shared across devices.  The plain one: none of them -- the stamps and
+// the trace compile to nothing, the inject test is gone and every scope is the
+// agent's.  launch_engine starts the plain one only for a launch that uses
+// none of these (EngineArgs::general).  The bounded waits and their reports
+// are in both.
+template <bool kPlainMode>
+struct EngineMode {
+  static constexpr bool kPlain = kPlainMode;
+  // FrameArgs::sys of a view, as this instantiation sees it
+  __device__ static __forceinline__ bool sys(int s) { return !kPlain && s != 0; }
+  // a diagnostic buffer (stamps, istamps, trace): never there in the plain engine
+  template <class T>
+  __device__ static __forceinline__ T* diag(T* p) {
+    return kPlain ? nullptr : p;
+  }
+};
+
 // Diagnostic live trace (mapped host memory, system scope): word k of this workgroup.
+template <class M>
 __device__ __forceinline__ void trace(int32_t* t, int k, int v) {
-  if (t && threadIdx.x == 0)
-    __hip_atomic_store(&t[blockIdx.x * 4 + k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if constexpr (!M::kPlain) {
+    if (t && threadIdx.x == 0)
+      __hip_atomic_store(&t[blockIdx.x * 4 + k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
 }
 
 // Plane pl (0 Y, 1 U, 2 V) of a plane set.  The three pointers are read as
@@ -172,10 +195,16 @@ __device__ __forceinline__ int fresh(int v) {
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Diagnostic timestamp (100 MHz constant clock) of phase k of macroblock mb.
+template <class M>
 __device__ __forceinline__ void stamp(uint64_t* stamps, int mb, int k) {
-  if (stamps && threadIdx.x == 0) stamps[(size_t)mb * kStampPhases + k] = __builtin_amdgcn_s_memrealtime();
+  if constexpr (!M::kPlain) {
+    if (stamps && threadIdx.x == 0) stamps[(size_t)mb * kStampPhases + k] = __builtin_amdgcn_s_memrealtime();
+  }
 }
-__device__ __forceinline__ void stamp(FA& a, int mb, int k) { stamp(a.stamps, mb, k); }
+template <class M>
+__device__ __forceinline__ void stamp(FA& a, int mb, int k) {
+  if constexpr (!M::kPlain) stamp<M>(a.stamps, mb, k);
+}
 
 // Time accounting (kernels.h Acct; CAIRO_ACCT=1 builds with cairo_ctx_set_debug
 // 32): thread 0 adds 10 ns ticks to its workgroup's shard (posted atomics).
@@ -219,15 +248,18 @@ __device__ __forceinline__ uint64_t tagged(uint32_t epoch, int cols) {
 __device__ __forceinline__ uint64_t progress_at(const uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// The previous frame's words may live on another device (FrameArgs::sys).
-__device__ __forceinline__ uint64_t progress_peer(bool sys, const uint64_t* p) {
-  return sys ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-             : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// The previous frame's words may live on another device (sys = FrameArgs::sys;
+// never in the plain engine: M::sys).
+template <class M>
+__device__ __forceinline__ uint64_t progress_peer(int sys, const uint64_t* p) {
+  return M::sys(sys) ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
+                     : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // Acquire after a wait (thread 0): agent scope, or system scope when the data
 // released by the observed word may come from another device.
-__device__ __forceinline__ void acquire_fence(bool sys) {
-  if (sys)
+template <class M>
+__device__ __forceinline__ void acquire_fence(int sys) {
+  if (M::sys(sys))
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
   else
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -281,9 +313,10 @@ __device__ __forceinline__ void wait_records(FA& a, int row, int group) {
 
 // Consumer side of a hand-off: one lane waited; invalidate this CU's L1 and
 // let every wave load only after the barrier (MI355X_MICROARCH.md, Valid forms).
-__device__ __forceinline__ void acquire_after_wait(bool sys = false) {
+template <class M>
+__device__ __forceinline__ void acquire_after_wait(int sys) {
   if (threadIdx.x == 0) {
-    acquire_fence(sys);
+    acquire_fence<M>(sys);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
@@ -958,6 +991,7 @@ __device__ __forceinline__ int wg_broadcast(volatile int* slot, int v) {
 struct DbLds;
 struct DbState;
 __device__ __forceinline__ bool deblock_chunk_ready(FA& a, int r, const DbState& st);
+template <class M>
 __device__ __forceinline__ void deblock_chunk(FA& a, int r, DbLds& D, DbState& st, bool known_ready = false);
 __device__ __forceinline__ bool deblock_pending(FA& a, const DbState& st);
 
@@ -979,7 +1013,7 @@ __device__ __forceinline__ int inter_need_cols(FA& a, int g, int level) {
 // grow, so a "full" seen here stays true; the acquire at the wait's exit
 // follows these loads too.  Written before the exit's barrier, so it is
 // workgroup-uniform after the wait; 0 when the wait gave up.
-template <bool kDeblock = true>
+template <class M, bool kDeblock = true>
 __device__ __forceinline__ void helper_wait(FA& a, int back, int r, int rr, int need, DbLds& D, DbState& st,
                                             int* flag, int* full2 = nullptr, bool want_full = false,
                                             int g = 0) {
@@ -993,14 +1027,14 @@ __device__ __forceinline__ void helper_wait(FA& a, int back, int r, int rr, int 
     if (threadIdx.x == 0) {
       // the progress poll, the level-2 words and the deblock readiness loads
       // in flight together
-      const uint64_t pv = pp ? progress_peer(a.sys, pp + rr) : ~0ull;
+      const uint64_t pv = pp ? progress_peer<M>(a.sys, pp + rr) : ~0ull;
       uint64_t w3 = ~0ull, w2 = ~0ull;
       if (want_full && pp) {
-        w3 = progress_peer(a.sys, pp + min(r + 3, a.hmb - 1));
-        w2 = progress_peer(a.sys, pp + min(r + 2, a.hmb - 1));
+        w3 = progress_peer<M>(a.sys, pp + min(r + 3, a.hmb - 1));
+        w2 = progress_peer<M>(a.sys, pp + min(r + 2, a.hmb - 1));
       }
       const bool dbr = kDeblock && deblock_pending(a, st) && deblock_chunk_ready(a, r, st);
-      if (a.inject && r == min(1, a.hmb - 1)) {  // test hook: this wait "times out" at once
+      if (!M::kPlain && a.inject && r == min(1, a.hmb - 1)) {  // test hook: this wait "times out" at once
         report_timeout(a, kWaitInjected, r, need, rr | (back << 16), pv);
         d = 1;
         if (want_full) *full2 = 0;
@@ -1029,12 +1063,12 @@ __device__ __forceinline__ void helper_wait(FA& a, int back, int r, int rr, int 
     if (d == 1) break;
     if (kDeblock && d == 2) {
       const uint64_t tb = acct_now();
-      deblock_chunk(a, r, D, st, true);
+      deblock_chunk<M>(a, r, D, st, true);
       tdb += acct_now() - tb;
     }
   }
   if (threadIdx.x == 0) {  // the check used a relaxed load: acquire what it observed
-    acquire_fence(a.sys);
+    acquire_fence<M>(a.sys);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
@@ -1164,8 +1198,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) u32x4 gbl_u32x4;
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef u32x2 u32x2_u __attribute__((aligned(2)));  // four int16 of a plane row, at any even address
-__device__ __forceinline__ void store16_through(bool sys, int16_t* p, u32x4 v) {
-  if (sys)
+template <class M>
+__device__ __forceinline__ void store16_through(int sys, int16_t* p, u32x4 v) {
+  if (M::sys(sys))
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
   else
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
@@ -1223,8 +1258,9 @@ __device__ __forceinline__ ptrdiff_t carry_chunk(FA& a, int r, int g, int& pl) {
 __device__ __forceinline__ u32x4 carry_load(FA& a, int pl, ptrdiff_t off) {
   return *(const gbl_u32x4*)(pick(planes(a.coef_prev), pl) + off);
 }
+template <class M>
 __device__ __forceinline__ void carry_store(FA& a, int pl, ptrdiff_t off, u32x4 v) {
-  store16_through(a.sys, pick(planes(a.coef), pl) + off, v);
+  store16_through<M>(a.sys, pick(planes(a.coef), pl) + off, v);
 }
 
 // Reference offset `off` of group g of row r: the tagged records of the
@@ -1243,10 +1279,11 @@ __device__ __forceinline__ void carry_store(FA& a, int pl, ptrdiff_t off, u32x4 
 // barrier either.  Reference 1 issues the carry's load, the zero-MV loads and
 // that poll before it waits for any of them.
 // Returns whether any wave searched (workgroup-uniform).
-template <bool kRef1>
+template <class M, bool kRef1>
 __device__ __forceinline__ bool inter_task(FA& a0, int r, int g, int off, InterLds& L, DbLds& D, DbState& st,
-                                           int* flag, uint64_t* is, bool carried = false) {
+                                           int* flag, uint64_t* is0, bool carried = false) {
   FA& a = *opaque_view(&a0);
+  uint64_t* const is = M::diag(is0);  // the group's istamps (thread 0 of a stamped launch)
   ASM_MARK("group_start begin");
   const uint64_t tg0 = acct_now();
   const int wave = uni(threadIdx.x >> 6);  // scalar: the acceptance replay runs on SGPRs
@@ -1295,14 +1332,14 @@ __device__ __forceinline__ bool inter_task(FA& a0, int r, int g, int off, InterL
     const bool poll = threadIdx.x == 0 && !wf;
     uint64_t w3 = 0, w2 = 0;
     if (poll) {
-      w3 = progress_peer(a.sys, pp + min(r + 3, a.hmb - 1));
-      w2 = progress_peer(a.sys, pp + min(r + 2, a.hmb - 1));
+      w3 = progress_peer<M>(a.sys, pp + min(r + 3, a.hmb - 1));
+      w2 = progress_peer<M>(a.sys, pp + min(r + 2, a.hmb - 1));
     }
     // nothing of the batch is used above this line, so every load of it is
     // issued before the first wait (the compiler otherwise unpacks the luma
     // load, and waits for it, in front of the chroma loads)
     asm volatile("" : "+v"(cv), "+v"(zy), "+v"(zu), "+v"(zv), "+v"(w3), "+v"(w2));
-    if (coff >= 0) carry_store(a, cpl, coff, cv);
+    if (coff >= 0) carry_store<M>(a, cpl, coff, cv);
     Px6 zref;
     zref.y0 = (int16_t)zy.x, zref.y1 = (int16_t)(zy.x >> 16), zref.y2 = (int16_t)zy.y, zref.y3 = (int16_t)(zy.y >> 16);
     zref.u = zu, zref.v = zv;
@@ -1322,7 +1359,7 @@ __device__ __forceinline__ bool inter_task(FA& a0, int r, int g, int off, InterL
       if (poll) {
         f = (w3 >= want) & (w2 >= want);
         if (f) {  // acquire what the progress words released (the loads below follow the barrier)
-          acquire_fence(a.sys);
+          acquire_fence<M>(a.sys);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         acct_start(a.acct, Acct::kFallbackFull, f);
@@ -1346,11 +1383,11 @@ __device__ __forceinline__ bool inter_task(FA& a0, int r, int g, int off, InterL
     if (any && !wf) {  // (workgroup-uniform) the poll, as before the wait reported
       if (threadIdx.x == 0) {
         // both words loaded before either is tested (one round trip)
-        const uint64_t w3 = progress_peer(a.sys, pp + min(r + 3, a.hmb - 1));
-        const uint64_t w2 = progress_peer(a.sys, pp + min(r + 2, a.hmb - 1));
+        const uint64_t w3 = progress_peer<M>(a.sys, pp + min(r + 3, a.hmb - 1));
+        const uint64_t w2 = progress_peer<M>(a.sys, pp + min(r + 2, a.hmb - 1));
         const int f = (w3 >= want) & (w2 >= want);
         if (f) {
-          acquire_fence(a.sys);
+          acquire_fence<M>(a.sys);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         acct_start(a.acct, Acct::kFallbackFull, f);
@@ -1403,7 +1440,7 @@ __device__ __forceinline__ bool inter_task(FA& a0, int r, int g, int off, InterL
           acct_start(a.acct, Acct::kLvl2Runs, 1);
           // (no deblock meanwhile: rare, and its inputs' registers would spill
           // the search state live here)
-          helper_wait<false>(a, off == 1 ? 1 : 2, r, min(r + ((m & 2) ? 3 : 2), a.hmb - 1), inter_need_cols(a, g, 2),
+          helper_wait<M, false>(a, off == 1 ? 1 : 2, r, min(r + ((m & 2) ? 3 : 2), a.hmb - 1), inter_need_cols(a, g, 2),
                              D, st, flag);
           if (m & 2) stage_window(L.win, ref, a.wa, a.ha, ox, oy, kLvl1Rows, kWinL, 0, kWinLW);
           if (!lvl2c) stage_window(L.win, ref, a.wa, a.ha, ox, oy, 0, kLvl1Rows, kLvl1Cols, kWinLW);
@@ -1788,10 +1825,11 @@ __device__ __forceinline__ bool deblock_chunk_ready(FA& a, int r, const DbState&
 
 // Deblock chunk st.k of MB row r (whole workgroup; waits for its inputs, or
 // known_ready: deblock_chunk_ready said so).
+template <class M>
 __device__ __forceinline__ void deblock_chunk(FA& a0, int r, DbLds& D, DbState& st, bool known_ready) {
   FA& a = *opaque_view(&a0);
   const int tid = threadIdx.x;
-  const uint64_t tb = a.stamps && tid == 0 ? __builtin_amdgcn_s_memrealtime() : 0;
+  const uint64_t tb = !M::kPlain && a.stamps && tid == 0 ? __builtin_amdgcn_s_memrealtime() : 0;
   const uint64_t ta = acct_now();
   const PlaneSet cs = planes(a.recon[0]);
   const int cw = a.wa >> 1;
@@ -1987,14 +2025,14 @@ __device__ __forceinline__ void deblock_chunk(FA& a0, int r, DbLds& D, DbState& 
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (tid == 0) {
-        if (a.sys) {  // the next frame may read this row from another device
+        if (M::sys(a.sys)) {  // the next frame may read this row from another device
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
           __hip_atomic_store(&prog[r], above | (uint32_t)w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         } else {
           __hip_atomic_store(&prog[r], above | (uint32_t)w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-      if (a.stamps && tid == 0 && k < kDbStamps)
+      if (!M::kPlain && a.stamps && tid == 0 && k < kDbStamps)
         a.stamps[(size_t)a.wmb * a.hmb * kStampPhases + (size_t)r * kDbStamps + k] = __builtin_amdgcn_s_memrealtime();
       w0 = w1;
     }
@@ -2318,7 +2356,7 @@ __device__ __forceinline__ void coef_store_pair(FA& a, int e, int px, int py, in
 // quantize, reconstruct), left to right; whole workgroup.
 // kDecode: the decoder's reconstruction (decode_slice, decode.cpp:146-170) from
 // the given block table and coefficients, without the searches.
-template <bool kDecode>
+template <class M, bool kDecode>
 __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, int32_t* tr) {
   FA& a = a0;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -2342,10 +2380,11 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       const ViewCoderStart vs = view_block<ViewCoderStart>(ap);
       const uint64_t tp0 = acct_now();
       const int px = bx * kMB, mb = by * vs.wmb + bx;
-      trace(tr, 1, bx);
-      trace(tr, 2, (int)vs.epoch * 1000 + by);
-      stamp(ap->stamps, mb, 0);
-      if (ap->stamps && tid == 0) ap->stamps[(size_t)mb * kStampPhases + 10] = __builtin_amdgcn_s_memtime();
+      trace<M>(tr, 1, bx);
+      trace<M>(tr, 2, (int)vs.epoch * 1000 + by);
+      stamp<M>(*ap, mb, 0);
+      if (!M::kPlain && ap->stamps && tid == 0)
+        ap->stamps[(size_t)mb * kStampPhases + 10] = __builtin_amdgcn_s_memtime();
       // The row above's fresh column block (bx+2, by-1): its first granule
       // load is issued before the group-start wait below, so that a granule
       // already there costs no round trip after it (the tag is the flag: a
@@ -2411,7 +2450,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
           if (by_tag) rec_settle(*ap, vs.epoch, grec, gran_ld(grec), by, mb);
           else wait_records(*ap, by, bx >> 2);
         }
-        acquire_after_wait(ap->sys);  // the stale rows, references and previous output_cache
+        acquire_after_wait<M>(ap->sys);  // the stale rows, references and previous output_cache
         acct_add(ap->acct, Acct::kCoderGroupWait, acct_now() - tacc);
       }
       tacc = acct_now();
@@ -2448,7 +2487,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       if (early && tid == 0) {
         const ViewGroup gv = view_block<ViewGroup>(ap);
         ready0 = by_tag ? (uint32_t)(rd0 >> 32) == vs.epoch : (int)rd0 >= gv.nref;
-        if (ready0) acquire_fence(gv.sys);  // completes during the search; waited for after it
+        if (ready0) acquire_fence<M>(gv.sys);  // completes during the search; waited for after it
       }
       // source rows of this lane's group slot
       SrcRow s;  // biased u16 pairs (the encoder's source; unused when decoding)
@@ -2511,11 +2550,11 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       };
       const uint64_t tr0 = acct_now();
       if (!early) load_inter(vs);
-      stamp(ap->stamps, mb, 1);
+      stamp<M>(*ap, mb, 1);
       const uint64_t tr1 = acct_now();
       ASM_MARK("mb_start end");
       __syncthreads();
-      stamp(ap->stamps, mb, 2);
+      stamp<M>(*ap, mb, 2);
       tacc = acct_now();
       acct_add(ap->acct, Acct::kCoderRecords, tr1 - tr0);
       acct_add(ap->acct, Acct::kCoderPreBarrier, tacc - tr1);
@@ -2617,7 +2656,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
           acct_add(ap->acct, Acct::kSrchPasses, (uint64_t)passes);
           acct_add(ap->acct, Acct::kSrchPasses2 + (passes - 3), 1);
         }
-        stamp(*ap, mb, 3);
+        stamp<M>(*ap, mb, 3);
         if (!(CAIRO_ATTR_SKIP & 16)) {  // sub-pel (perform_intra_subpixel_motion_search, motion.cpp:277-317)
           ASM_MARK("subpel begin");
           const int bx0 = sel.bx, by0 = sel.by;
@@ -2648,7 +2687,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
           }
           ASM_MARK("subpel end");
         }
-        stamp(*ap, mb, 4);
+        stamp<M>(*ap, mb, 4);
         acct_add(ap->acct, Acct::kCoderSearch, acct_now() - tacc);
         if (early) {  // the group's records (and the cross-frame dependencies), then this MB's
           // the block again, not kept live across the search
@@ -2660,7 +2699,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
               const uint64_t* gr = (const uint64_t*)&ws.inter_desc[mb];
               if (ws.nrec) rec_settle(*aq, ws.epoch, gr, gran_ld(gr), by, mb);
               else wait_records(*aq, by, bx >> 2);
-              acquire_fence(aq->sys);
+              acquire_fence<M>(aq->sys);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the acquire has completed
           }
@@ -2713,7 +2752,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       const ViewCoderStart ps = view_block<ViewCoderStart>(ap);  // for the stores and the publish
       const uint32_t tag = ps.epoch;
       const int cw = ps.wa >> 1;
-      stamp(*ap, mb, 5);
+      stamp<M>(*ap, mb, 5);
       const uint64_t tx5 = acct_now();
       // this lane's source elements for the residual, loaded after the
       // searches: live across them, they pushed the engine into scratch
@@ -2767,7 +2806,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
                    : (__ballot(res != 0) ? fdct_lane(&L.bufA[b * 64], &L.bufB[b * 64], lane, res) : 0);
         }
       }
-      stamp(*ap, mb, 6);
+      stamp<M>(*ap, mb, 6);
       // The prefetched window blocks for MB bx+1 (loaded before the search),
       // into the window before this macroblock's first store: settled after
       // the stores, their wait (vmcnt retires in order) also waited for the
@@ -2838,7 +2877,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
             coef_store_pair(*ap, (wave + 4 * bi) * 64 + lane, px, py, cp[bi]);
         }
       }
-      stamp(*ap, mb, 7);
+      stamp<M>(*ap, mb, 7);
       const uint64_t tx7 = acct_now();
       asm volatile("" ::: "memory");  // program order: the coefficient stores, then (kStoresAfterCoef) ...
       // publish first (the next row's coder waits for exactly these): pixel
@@ -2859,7 +2898,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
                   ((uint64_t)tag << 32) | ((uint32_t)pv[bi] & 0xFFFFu) | ((uint32_t)nb << 16));
         }
       }
-      stamp(*ap, mb, 8);
+      stamp<M>(*ap, mb, 8);
       // reconstruction -> the window (the slot is written by the deblock,
       // from the granules)
       _Pragma("unroll") for (int bi = 0; bi < 2; bi++) if (bi < nblk) {
@@ -2892,7 +2931,7 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
       if (tid == 0)
         gran_st(gran_at(ps.granules, ps.wmb, bx, by, kGranulesPerMB),
                 ((uint64_t)tag << 32) | ((d.block_type & kCopy) ? 0x100u : 0u) | d.q_index);
-      stamp(*ap, mb, 9);
+      stamp<M>(*ap, mb, 9);
       if (CAIRO_ACCT) {
         const uint64_t tx9 = acct_now();
         acct_add(ap->acct, Acct::kCoderXform, tx7 - tx5);
@@ -2902,7 +2941,8 @@ __device__ __forceinline__ void code_row(FA& a0, int by, RowLds& L, int* flag, i
         acct_add(ap->acct, Acct::kCoderPublish, tx8 - tx7);
         acct_add(ap->acct, Acct::kCoderDrain, tx9 - tx8);
       }
-      if (ap->stamps && tid == 0) ap->stamps[(size_t)mb * kStampPhases + 11] = __builtin_amdgcn_s_memtime();
+      if (!M::kPlain && ap->stamps && tid == 0)
+        ap->stamps[(size_t)mb * kStampPhases + 11] = __builtin_amdgcn_s_memtime();
       more = bx + 1 < ps.wmb;
       ASM_MARK("mb_publish end");
     }
@@ -2930,6 +2970,7 @@ struct EngineLds {
 // coder waits for exactly these), and the deblock of row r, chunk by chunk as
 // the coder's granules arrive (advanced whenever the inter search is waiting
 // or done).  Never blocks on its own row coder while an inter group is due.
+template <class M>
 __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* flag, int32_t* tr) {
   FA& a = a0;
   const int tid = threadIdx.x;
@@ -2938,9 +2979,9 @@ __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* fla
   DbState st{0, 0, 0, 8};
   for (int g = 0; g < a0.ng; g++) {
     FA& a = *opaque_view(&a0);
-    trace(tr, 1, g);
-    trace(tr, 2, (int)a.epoch * 1000 + r);
-    uint64_t* is = a.istamps && tid == 0 ? a.istamps + (size_t)(r * a.ng + g) * kIStamps : nullptr;
+    trace<M>(tr, 1, g);
+    trace<M>(tr, 2, (int)a.epoch * 1000 + r);
+    uint64_t* is = !M::kPlain && a.istamps && tid == 0 ? a.istamps + (size_t)(r * a.ng + g) * kIStamps : nullptr;
     if (is) is[0] = __builtin_amdgcn_s_memrealtime(), is[3] = is[4] = is[5] = is[6] = is[7] = is[8] = is[9] = is[10] = 0;
     // The older references (offsets 2..R-1) first: frame index-2 is final
     // over the group's level-1 window long before the previous frame is (its
@@ -2952,28 +2993,28 @@ __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* fla
     if (a.inter) group_source(a, r, g, L.inter);
     if (a.inter && a.nref >= 2) {
       // (the wait also says whether the whole window is final: §4.12)
-      helper_wait(a, 2, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag, &L.inter.wfull[1], true,
+      helper_wait<M>(a, 2, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag, &L.inter.wfull[1], true,
                   g);
       const uint64_t ts = acct_now();
       zero_mv_older(a, r, g, L.inter);
       for (int off = 2; off <= a.nref; off++)
-        searched |= inter_task<false>(a, r, g, off, L.inter, L.db, st, flag, is);
+        searched |= inter_task<M, false>(a, r, g, off, L.inter, L.db, st, flag, is);
       acct_add(a.acct, Acct::kHelperSearch, acct_now() - ts);
     }
     // level 1 of the group's window in the previous frame; deblock meanwhile
     // (leaving the chunks to the catch-up after the group's records instead
     // measured neutral in round 4; catch-ups between the older references'
     // searches too, in round 5)
-    helper_wait(a, 1, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag,
+    helper_wait<M>(a, 1, r, min(r + 2, a.hmb - 1), inter_need_cols(a, g, 1), L.db, st, flag,
                 &L.inter.wfull[0], a.inter != 0, g);
     if (is) is[1] = __builtin_amdgcn_s_memrealtime();
-    trace(tr, 3, 50);
+    trace<M>(tr, 3, 50);
     if (a.inter) {
       // the group's output_cache carry, after the wait (which covers
       // coef_prev: carry_chunk), inside inter_task's first batch of loads;
       // released by inter_task before the records
       const uint64_t ts = acct_now();
-      searched |= inter_task<true>(a, r, g, 1, L.inter, L.db, st, flag, is, carry_wanted(a));
+      searched |= inter_task<M, true>(a, r, g, 1, L.inter, L.db, st, flag, is, carry_wanted(a));
       acct_add(a.acct, Acct::kHelperSearch, acct_now() - ts);
       if (!searched) {
         acct_start(a.acct, Acct::kIdleGroups, 1);
@@ -2993,20 +3034,20 @@ __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* fla
       if (tid == 0) d = st.k < nch && deblock_chunk_ready(a, r, st);
       if (!wg_broadcast(vflag, d)) break;
       const uint64_t tb = acct_now();
-      deblock_chunk(a, r, L.db, st, true);
+      deblock_chunk<M>(a, r, L.db, st, true);
       tcdb += acct_now() - tb;
       caught++;
     }
     acct_add(a.acct, Acct::kHelperCatchup, acct_now() - tc - tcdb);
     if (is) is[11] = ((uint64_t)caught << 32) | (uint32_t)(__builtin_amdgcn_s_memrealtime() - is[2]);
   }
-  trace(tr, 1, 1000);
+  trace<M>(tr, 1, 1000);
   // The rest of the row trails its coder: one lane polls each chunk's
   // readiness (row r-1's progress and the chunk's last info granule, with
   // back-off) while the other waves sit at the barrier, instead of every
   // lane of the chunk's loads re-polling its own granule.
   while (st.k < nch) {
-    trace(tr, 3, 60000 + st.k);
+    trace<M>(tr, 3, 60000 + st.k);
     int d = 0;
     if (tid == 0) {
       const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
@@ -3017,10 +3058,10 @@ __device__ __forceinline__ void row_helper(FA& a0, int r, HelperLds& L, int* fla
         __builtin_amdgcn_s_sleep(kWaitSleep);
       }
     }
-    deblock_chunk(a, r, L.db, st, wg_broadcast(vflag, d) != 0);
+    deblock_chunk<M>(a, r, L.db, st, wg_broadcast(vflag, d) != 0);
   }
-  trace(tr, 3, 100000);
-  if (a.stamps && tid == 0) {  // the row's deblock times, in per-row stamp slots no chunk uses at these widths
+  trace<M>(tr, 3, 100000);
+  if (!M::kPlain && a.stamps && tid == 0) {  // the row's deblock times, in per-row stamp slots no chunk uses at these widths
     uint64_t* ds = a.stamps + (size_t)a.wmb * a.hmb * kStampPhases + (size_t)r * kDbStamps;
     ds[kDbStamps - 1] = st.busy;
   }
@@ -3172,12 +3213,14 @@ __device__ __forceinline__ void task_done(int32_t* sync) {
   }
 }
 
-template <bool kDecode>
+// kPlain: the plain instantiation (EngineMode); launch_engine chooses.
+template <bool kDecode, bool kPlain>
 __global__ __launch_bounds__(256, 3) void k_engine(EngineArgs e) {
+  typedef EngineMode<kPlain> M;
   __shared__ EngineLds L;
   load_tables();
   const int b = blockIdx.x, hmb = e.hmb;
-  uint64_t* ks = e.stamps ? e.stamps + (size_t)kMaxBatch * stamp_frame_words(e.wmb, hmb) : nullptr;
+  uint64_t* ks = !M::kPlain && e.stamps ? e.stamps + (size_t)kMaxBatch * stamp_frame_words(e.wmb, hmb) : nullptr;
   if (ks && threadIdx.x == 0)
     __hip_atomic_fetch_min(&ks[0], __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   bool helper;
@@ -3193,14 +3236,14 @@ __global__ __launch_bounds__(256, 3) void k_engine(EngineArgs e) {
       const int t = next_task(e, 0, lab, L, prev);
       acct_add(e.acct, Acct::kHelperDequeue, acct_now() - tq);
       if (t < 0) break;
-      trace(e.trace, 0, 1000000 + t);
+      trace<M>(e.trace, 0, 1000000 + t);
       const int32_t o = (prev ? e.porder : e.order)[0][t];
       const uint64_t tt = acct_now();
-      row_helper(((FA*)(prev ? e.pfa : e.fa))[uni(o >> 16)], o & 0xFFFF, L.u.helper, &L.flag, e.trace);
+      row_helper<M>(((FA*)(prev ? e.pfa : e.fa))[uni(o >> 16)], o & 0xFFFF, L.u.helper, &L.flag, e.trace);
       task_done(prev ? e.psync : e.sync);
       acct_add(e.acct, Acct::kHelperTotal, acct_now() - tt);
       acct_add(e.acct, Acct::kHelperTasks, 1);
-      trace(e.trace, 0, 2000000 + t);
+      trace<M>(e.trace, 0, 2000000 + t);
     }
   } else {
     for (;;) {
@@ -3209,15 +3252,15 @@ __global__ __launch_bounds__(256, 3) void k_engine(EngineArgs e) {
       const int t = next_task(e, 1, lab, L, prev);
       acct_add(e.acct, Acct::kCoderDequeue, acct_now() - tq);
       if (t < 0) break;
-      trace(e.trace, 0, 3000000 + t);
+      trace<M>(e.trace, 0, 3000000 + t);
       const int32_t o = (prev ? e.porder : e.order)[1][t];
       const uint64_t tt = acct_now();
-      code_row<kDecode>(((FA*)(prev ? e.pfa : e.fa))[uni(o >> 16)], o & 0xFFFF, L.u.row, &L.flag, e.trace);
+      code_row<M, kDecode>(((FA*)(prev ? e.pfa : e.fa))[uni(o >> 16)], o & 0xFFFF, L.u.row, &L.flag, e.trace);
       task_done(prev ? e.psync : e.sync);
       acct_add(e.acct, Acct::kCoderTotal, acct_now() - tt);
       acct_add(e.acct, Acct::kCoderTasks, 1);
       acct_add(e.acct, Acct::kCoderMBs, (uint64_t)e.wmb);
-      trace(e.trace, 0, 4000000 + t);
+      trace<M>(e.trace, 0, 4000000 + t);
     }
   }
   if (ks && threadIdx.x == 0)
@@ -3295,8 +3338,17 @@ FrameArgs make_frame_view(const EngineArgs& e, const FrameDesc& f, int j) {
   return a;
 }
 
+// The smaller occupancy of the encode instantiations a context may launch
+// (plain or general, by launch): the pools are sized once, at create.
 hipError_t engine_blocks_per_cu(int* n) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, reinterpret_cast<const void*>(&k_engine<false>), 256, 0);
+  int plain = 0, general = 0;
+  hipError_t r = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &plain, reinterpret_cast<const void*>(&k_engine<false, true>), 256, 0);
+  if (r != hipSuccess) return r;
+  r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&general, reinterpret_cast<const void*>(&k_engine<false, false>),
+                                                   256, 0);
+  *n = plain < general ? plain : general;
+  return r;
 }
 
 // One wave: thread 0 polls the batch's finished-task count.
@@ -3321,10 +3373,13 @@ hipError_t launch_batch_wait(int32_t* sync, int tasks, int32_t* sticky, hipStrea
 }
 
 hipError_t launch_engine(const EngineArgs& e, hipStream_t s) {
+  // (a decode launch has the general instantiation only: one engine less to compile)
   if (e.decode)
-    hipLaunchKernelGGL(k_engine<true>, dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
+    hipLaunchKernelGGL((k_engine<true, false>), dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
+  else if (e.general)
+    hipLaunchKernelGGL((k_engine<false, false>), dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
   else
-    hipLaunchKernelGGL(k_engine<false>, dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
+    hipLaunchKernelGGL((k_engine<false, true>), dim3(e.n_helpers + e.n_rows), dim3(256), 0, s, e);
   return hipGetLastError();
 }
 

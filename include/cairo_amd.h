@@ -548,6 +548,13 @@ CAIRO_API int cairo_ctx_read_table(cairo_ctx *ctx, uint8_t *table);
  * per MB, 100 MHz clock; cairo_ctx_read_stamps). */
 CAIRO_API int cairo_ctx_set_debug(cairo_ctx *ctx, int flags);
 CAIRO_API int cairo_ctx_read_stamps(cairo_ctx *ctx, uint64_t *out);
+/* Which instantiation of the engine the last launch enqueued by this context
+ * runs (no synchronization; 0 before the first launch): 0 the plain one (no
+ * diagnostics compiled in, agent-scope hand-offs only), 1 the general one --
+ * chosen for a launch with stamps, trace or the inject flag set, one whose
+ * frames (or those of the previous launch it shares queues with) belong to a
+ * group across devices or processes, and every decode launch. */
+CAIRO_API int cairo_ctx_engine_variant(cairo_ctx *ctx);
 /* Debug: flags & 4 keeps a live per-workgroup state trace of the engine in
  * mapped host memory; read it (n int32 words) without synchronizing.
  * flags & 8 (test hook) marks the device's sticky timeout word as if an

@@ -35,19 +35,23 @@ SHORT = {"k_convert_batch": "convert", "k_engine": "engine"}
 
 def per_kernel(path, counter=None):
     vals = {}
+    if not os.path.exists(path):  # a pass that was not taken
+        return vals
     for r in csv.DictReader(open(path)):
         if counter and r.get("Counter_Name") != counter:
             continue
         name = r["Kernel_Name"]
         for k, short in SHORT.items():
-            if f"::{k}(" in name or f"::{k}<false>(" in name:
+            # (the encode engine: k_engine<false>, and since DESIGN §4.19 k_engine<false, true> plain /
+            # k_engine<false, false> general)
+            if f"::{k}(" in name or f"::{k}<false>(" in name or f"::{k}<false, " in name:
                 vals.setdefault(short, []).append(float(r["Counter_Value"]))
     # drop the first dispatch of each kernel (warm-up: intra frame, cold caches)
     return {k: v[1:] if len(v) > 1 else v for k, v in vals.items()}
 
 
 SQ = ["SQ_WAVES", "SQ_WAVE_CYCLES", "SQ_BUSY_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY",
-      "SQ_ACTIVE_INST_VALU", "SQ_INSTS_VALU", "GRBM_GUI_ACTIVE"]
+      "SQ_ACTIVE_INST_VALU", "SQ_INSTS_VALU", "SQ_INSTS_SALU", "GRBM_GUI_ACTIVE"]
 
 
 def wave_states(path):
@@ -68,9 +72,10 @@ def wave_states(path):
     out = {"median_per_dispatch": med,
            "waiting_frac": med.get("SQ_WAIT_ANY", 0) / wc,
            "issue_stalled_frac": med.get("SQ_WAIT_INST_ANY", 0) / wc,
-           "issuing_frac": med.get("SQ_ACTIVE_INST_ANY", 0) / wc,
-           "valu_frac_of_wave_time": med.get("SQ_ACTIVE_INST_VALU", 0) / wc}
-    if "GRBM_GUI_ACTIVE" in med:
+           "issuing_frac": med.get("SQ_ACTIVE_INST_ANY", 0) / wc}
+    if "SQ_ACTIVE_INST_VALU" in med:
+        out["valu_frac_of_wave_time"] = med["SQ_ACTIVE_INST_VALU"] / wc
+    if "GRBM_GUI_ACTIVE" in med and "SQ_ACTIVE_INST_VALU" in med:
         cycles = med["GRBM_GUI_ACTIVE"] / 8.0
         out["valu_issue_frac_of_chip"] = med.get("SQ_ACTIVE_INST_VALU", 0) * 4.0 / (cycles * 256 * 4)
     return out
@@ -98,6 +103,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="timed launches of the profiled bench.py run")
     ap.add_argument("--batch", type=int, default=0,
                     help="frames per engine launch in the profiled run (0: the library default for --config)")
+    ap.add_argument("--out", default="", help="output json (default profiles/pmc_<config>[_<content>].json)")
+    ap.add_argument("--parent-src", default="",
+                    help="the same passes of the parent tree: its wave states and the per-frame instruction "
+                         "counts of both are added (engine_wave_states_parent, engine_insts_per_frame_millions)")
     a = ap.parse_args()
     if a.batch <= 0:
         sys.path.insert(0, ROOT)
@@ -129,10 +138,14 @@ def main():
         res["per_launch_hbm_bytes"][k] = int(round((2 * f + w) * 1024))
         res["per_frame_hbm_bytes"][k] = int(round((2 * f + w) * 1024 / a.batch))
         res["dispatches"][k] = min(len(fetch[k]), len(write[k]))
+    if not fetch and not write:  # an SQ pass alone (e.g. a before / after instruction count)
+        res["method"] = ("rocprofv3 --pmc over bench.py's hot path, one pass per tree in a run of its own, no tracing; "
+                         "the encode engine's dispatches, median over the dispatches after the first; per frame = "
+                         "per launch / frames per launch")
     trace = os.path.join(a.src, "prof_kt", "run_kernel_trace.csv")
     if os.path.exists(trace):  # the same figures as bench.py's roofline, from the dispatch timestamps
         iv = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(open(trace))
-                    if "::k_engine<false>(" in r["Kernel_Name"])
+                    if "::k_engine<false>(" in r["Kernel_Name"] or "::k_engine<false, " in r["Kernel_Name"])
         timed = iv[-a.steps:]  # bench.py's timed launches follow the warm-up ones (ctx.sync between)
         if timed:
             busy = union_ns(timed) / 1e6
@@ -222,7 +235,18 @@ def main():
     ws = wave_states(os.path.join(a.src, "prof_sq", "run_counter_collection.csv"))
     if ws:
         res["engine_wave_states"] = ws
-    path = os.path.join(out_dir, f"pmc_{a.config}{sfx}.json")
+    if a.parent_src:
+        pw = wave_states(os.path.join(a.parent_src, "prof_sq", "run_counter_collection.csv"))
+        if pw and ws:
+            res["engine_wave_states_parent"] = pw
+            ins = {}
+            for c in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_ACTIVE_INST_ANY", "SQ_WAIT_ANY"):
+                old, new = pw["median_per_dispatch"].get(c), ws["median_per_dispatch"].get(c)
+                if old and new:
+                    ins[c] = {"parent": round(old / a.batch / 1e6, 2), "change": round(new / a.batch / 1e6, 2),
+                              "percent": round(100.0 * (new - old) / old, 2)}
+            res["engine_insts_per_frame_millions"] = ins
+    path = a.out or os.path.join(out_dir, f"pmc_{a.config}{sfx}.json")
     json.dump(res, open(path, "w"), indent=1)
     print(json.dumps(res["per_launch_hbm_bytes"]))
 
