@@ -168,6 +168,7 @@ def lib() -> ctypes.CDLL:
         "cairo_task_order": (I, [I, I, P, ctypes.POINTER(I)]),
         "cairo_task_queues": (I, [I, I, I, I, I, P, P, ctypes.POINTER(I)]),
         "cairo_kat_transform": (I, [P, P, P, I, P, P, P, I]),
+        "cairo_kat_precode": (I, [U, U, U, I, I, P, P, P, P, P, U, P, P, ctypes.c_uint64, P, U, I]),
         "cairo_serialize_slice": (I, [P, U, U, U, P, P, P, P, U, ctypes.POINTER(U)]),
         "cairo_serialize_feed": (I, [P, ctypes.c_uint64, P, U, ctypes.POINTER(U)]),
         "cairo_precode_slice": (I, [P, U, U, U, P, P, P, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -1256,6 +1257,38 @@ def precode_slice(table: np.ndarray, wmb: int, hmb: int, ring: int, cy, cu, cv):
     _ck(L.cairo_precode_slice(_ptr(t), wmb, hmb, ring, _ptr(cy), _ptr(cu), _ptr(cv), _ptr(out), out.size,
                               ctypes.byref(nb)), "cairo_precode_slice")
     return out[: (nb.value + 31) // 32], nb.value
+
+
+FEED_HDR_WORDS = 16  # kFeedHdrWords (precode.h): bits lo, hi; overflow; dropped writes; 11 list starts; unused
+
+
+def kat_precode(frames, wmb: int, hmb: int, ring: int, slots=None, nslots: int | None = None, prefill: int = 0,
+                feed_words: int = 0, guard_words: int = 64, device: int = 0):
+    """The GPU precode on host tables and planes, without a context
+    (cairo_kat_precode): frames = [(table, (y, u, v)), ...] of one geometry in
+    one launch, frame j on staging slot slots[j] of nslots (default: j of
+    len(frames)), every buffer holding `prefill` before.
+    -> (hdr (n, 16), feed (n, feed_words): each frame's host words after the
+    header, guard (n, guard_words): its slot's device words from the feed's end
+    on)."""
+    n = len(frames)
+    slots = np.ascontiguousarray(np.arange(n) if slots is None else slots, dtype=np.int32)
+    nslots = n if nslots is None else nslots
+    mbs = wmb * hmb
+    tables = np.zeros((n, mbs * 16), np.uint8)
+    cy = np.zeros((n, hmb * 16, wmb * 16), np.int16)
+    cu = np.zeros((n, hmb * 8, wmb * 8), np.int16)
+    cv = np.zeros((n, hmb * 8, wmb * 8), np.int16)
+    for j, (table, (y, u, v)) in enumerate(frames):
+        tables[j] = np.ascontiguousarray(table).view(np.uint8)
+        cy[j], cu[j], cv[j] = y, u, v
+    hdr = np.zeros((n, FEED_HDR_WORDS), np.uint32)
+    feed = np.zeros((n, feed_words), np.uint32)
+    guard = np.zeros((n, guard_words), np.uint32)
+    _ck(lib().cairo_kat_precode(wmb, hmb, ring, n, nslots, _ptr(slots), _ptr(tables), _ptr(cy), _ptr(cu), _ptr(cv),
+                                prefill, _ptr(hdr), _ptr(feed) if feed_words else None, feed_words,
+                                _ptr(guard) if guard_words else None, guard_words, device), "cairo_kat_precode")
+    return hdr, feed, guard
 
 
 def unserialize_slice(payload: bytes, nbits: int, wmb: int, hmb: int, ring: int, table=None, planes=None,

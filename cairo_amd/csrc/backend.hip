@@ -2065,6 +2065,82 @@ int cairo_kat_transform(const int16_t* src, const int16_t* pred, const uint8_t* 
   return kSuccess;
 }
 
+int cairo_kat_precode(uint32_t wmb, uint32_t hmb, uint32_t ring, int count, int nslots, const int32_t* slot,
+                      const uint8_t* tables, const int16_t* coef_y, const int16_t* coef_u, const int16_t* coef_v,
+                      uint32_t prefill, uint32_t* hdr, uint32_t* feed, uint64_t feed_words, uint32_t* guard,
+                      uint32_t guard_words, int device) {
+  if (!slot || !tables || !coef_y || !coef_u || !coef_v || !hdr || (!feed && feed_words) || (!guard && guard_words) ||
+      count < 1 || count > kMaxBatch || nslots < count || nslots > kMaxBatch || !wmb || !hmb ||
+      (uint64_t)wmb * hmb > 65535u || ring < 1 || ring > (uint32_t)kMaxRing)
+    return kInvalidArg;
+  for (int j = 0; j < count; j++) {
+    if (slot[j] < 0 || slot[j] >= nslots) return kInvalidArg;
+    for (int i = 0; i < j; i++)
+      if (slot[i] == slot[j]) return kInvalidArg;
+  }
+  CK(hipSetDevice(device));
+  const size_t mbs = (size_t)wmb * hmb, ny = mbs * 256, nc = mbs * 64, ne = ny + 2 * nc;
+  const size_t stride = feed_words_per_slot(mbs), sw = feed_scratch_words(mbs), hw = kFeedHdrWords + stride;
+  const size_t take = feed_words < stride ? (size_t)feed_words : stride;
+  KatBuffer dt, dc, dfa, dfeed, dhdr, dscr, dhost;  // dhost stands for the frames' mapped pinned host buffers
+  int r;
+  if ((r = dt.alloc(count * mbs * sizeof(BlockDesc))) || (r = dc.alloc(count * ne * 2)) ||
+      (r = dfa.alloc(count * sizeof(FrameArgs))) || (r = dfeed.alloc(nslots * stride * 4)) ||
+      (r = dhdr.alloc((size_t)nslots * kFeedHdrWords * 4)) || (r = dscr.alloc(nslots * sw * 4)) ||
+      (r = dhost.alloc(count * hw * 4)) || (r = dt.upload(tables, count * mbs * sizeof(BlockDesc))))
+    return r;
+  // the views: only what the precode reads of them
+  std::vector<FrameArgs> views((size_t)count);
+  FeedArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  for (int j = 0; j < count; j++) {
+    int16_t* base = dc.as<int16_t>() + (size_t)j * ne;
+    if ((r = dc.upload(coef_y + (size_t)j * ny, ny * 2, (size_t)j * ne * 2)) ||
+        (r = dc.upload(coef_u + (size_t)j * nc, nc * 2, ((size_t)j * ne + ny) * 2)) ||
+        (r = dc.upload(coef_v + (size_t)j * nc, nc * 2, ((size_t)j * ne + ny + nc) * 2)))
+      return r;
+    FrameArgs& a = views[(size_t)j];
+    memset((void*)&a, 0, sizeof(a));
+    a.wa = (int)wmb * 16, a.ha = (int)hmb * 16, a.wmb = (int)wmb, a.hmb = (int)hmb, a.ring = (int)ring;
+    a.table = dt.as<BlockDesc>() + (size_t)j * mbs;
+    a.coef = PlaneSet{base, base + ny, base + ny + nc};
+    fa.slot[j] = slot[j];
+    fa.host[j] = dhost.as<uint32_t>() + (size_t)j * hw;
+  }
+  if ((r = dfa.upload(views.data(), count * sizeof(FrameArgs)))) return r;
+  // what the slots held before: every feed word, header, scratch word and host word
+  CK(hipMemsetD32(dfeed.as<void>(), (int)prefill, nslots * stride));
+  CK(hipMemsetD32(dhdr.as<void>(), (int)prefill, (size_t)nslots * kFeedHdrWords));
+  CK(hipMemsetD32(dscr.as<void>(), (int)prefill, nslots * sw));
+  CK(hipMemsetD32(dhost.as<void>(), (int)prefill, count * hw));
+  // the launch as enqueue_results makes it (no table or timeout hand-over)
+  fa.nframes = count;
+  fa.fa = dfa.as<FrameArgs>();
+  fa.scratch = dscr.as<uint32_t>();
+  fa.scratch_stride = sw;
+  fa.feed = dfeed.as<uint32_t>();
+  fa.feed_stride = stride;
+  fa.hdr = dhdr.as<uint32_t>();
+  if ((r = fail(launch_precode(fa, (int)mbs, nullptr), "precode")) ||
+      (r = kat_run(launch_feed_copy(fa, nullptr), "k_feed_copy")))
+    return r;
+  for (int j = 0; j < count; j++) {
+    uint32_t* h = hdr + (size_t)j * kFeedHdrWords;
+    if ((r = dhost.download(h, kFeedHdrWords * 4, (size_t)j * hw * 4)) ||
+        (take && (r = dhost.download(feed + (size_t)j * feed_words, take * 4, ((size_t)j * hw + kFeedHdrWords) * 4))))
+      return r;
+    for (size_t i = take; i < feed_words; i++) feed[(size_t)j * feed_words + i] = prefill;
+    // the slot's device words from the frame's end on (from word 0 where nothing was written)
+    const uint64_t bits = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
+    const uint64_t end = h[2] ? 0 : (bits + 31) / 32;
+    const size_t n = end >= stride ? 0 : (stride - end < guard_words ? (size_t)(stride - end) : guard_words);
+    uint32_t* g = guard + (size_t)j * guard_words;
+    if (n && (r = dfeed.download(g, n * 4, ((size_t)slot[j] * stride + end) * 4))) return r;
+    for (size_t i = n; i < guard_words; i++) g[i] = prefill;
+  }
+  return kSuccess;
+}
+
 int cairo_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

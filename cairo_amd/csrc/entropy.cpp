@@ -63,10 +63,12 @@ struct CodeTables {
     for (int i = 0; i < 65536; i++) {
       const int16_t v = (int16_t)i;
       uint32_t len;
-      const uint32_t val = v == 0 ? 1u : (((uint32_t)iabs(v) << 1) | (uint32_t)((v >> 15) & 1));
+      // |-32768| = 32767 (the reference defines nothing there; precode.hip se_val does the same),
+      // so every code has at most 31 bits
+      const uint32_t val = v == 0 ? 1u : (((uint32_t)(v == INT16_MIN ? INT16_MAX : iabs(v)) << 1) | (uint32_t)((v >> 15) & 1));
       const uint64_t c = golomb(val, &len);
-      se_code[i] = (uint32_t)c;  // |v| = 32768 would need 33 bits; never produced
-      se_len[i] = (uint8_t)(len > 32 ? 32 : len);
+      se_code[i] = (uint32_t)c;
+      se_len[i] = (uint8_t)len;
     }
     for (int r = 0; r <= 64; r++) {
       uint32_t len;

@@ -70,7 +70,10 @@ extern "C" {
  *      except the scaled submit.  Nothing existing changes.
  *   4  (unchanged) the scaled tensor submit adds entry points only:
  *      cairo_tensor_scale_check, cairo_ctx_submit_tensor_scaled,
- *      cairo_stream_submit_tensor_scaled, cairo_kat_tensor_scale. */
+ *      cairo_stream_submit_tensor_scaled, cairo_kat_tensor_scale.
+ *   4  (unchanged) cairo_kat_precode is added.  The host precode codes a value
+ *      of -32768 as -32767 (31 bits, as the GPU precode always did) where it
+ *      used to write 32 bits of a 33-bit code; no encoder produces the value. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -761,6 +764,30 @@ CAIRO_API int cairo_kat_metrics(uint32_t w, uint32_t h, uint32_t pitch_elems, co
 CAIRO_API int cairo_kat_transform(const int16_t *src, const int16_t *pred, const uint8_t *qtype,
                                   int count, int16_t *coef, int16_t *recon, int32_t *qvar,
                                   int device);
+
+/* Known-answer check of the GPU entropy precode (the kernels behind
+ * CAIRO_OUT_FEED) on host buffers, without a context or the engine: count
+ * frames (1..48, the most one launch holds) of wmb x hmb macroblocks (at most
+ * 65535) and ring 1..4, frame j's block table at tables + j * wmb * hmb * 16
+ * and its coefficient planes (pitch wmb * 16, chroma wmb * 8) at
+ * coef_y + j * wmb * hmb * 256 and coef_u / coef_v + j * wmb * hmb * 64.  The
+ * tables need not be legal: the precode reads what the serializer reads.
+ * Frame j uses staging slot slot[j] of nslots (count <= nslots <= 48; the
+ * slots distinct).  Every slot's device feed buffer, header and scratch, and
+ * every frame's host buffer, hold the word `prefill` before the launch, which
+ * is the one a context makes for a batch (precode, then the copy to the host
+ * buffers).  Out, per frame: hdr[16] as copied (bits lo, hi; overflow flag;
+ * dropped writes; the start bit of each of the 11 lists; one unused word);
+ * the first feed_words words of its host buffer after the header, copied or
+ * still `prefill`; and guard_words words of its slot's device feed buffer from
+ * word (bits + 31) / 32 on -- from word 0 when the overflow flag is set -- with
+ * `prefill` for words beyond the slot's end: one zeroed word (none on
+ * overflow), then words no kernel may have touched. */
+CAIRO_API int cairo_kat_precode(uint32_t wmb, uint32_t hmb, uint32_t ring, int count, int nslots,
+                                const int32_t *slot, const uint8_t *tables, const int16_t *coef_y,
+                                const int16_t *coef_u, const int16_t *coef_v, uint32_t prefill, uint32_t *hdr,
+                                uint32_t *feed, uint64_t feed_words, uint32_t *guard, uint32_t guard_words,
+                                int device);
 
 /* Known-answer check of the pixel-format kernels on host buffers, without a
  * context or the engine.  dir 0: frame (fmt, pitch) -> tight int16 planes (w

@@ -839,18 +839,45 @@ uint32_t orc_abac_feed(const uint32_t *words, uint64_t nbits, uint8_t *out, uint
 /* The feed stream (common.cpp:147) only bounds how many bits one section may
  * write between empty() calls; every accepted bit is consumed by the coder
  * in order.  Writes that would exceed capacity are dropped whole
- * (bitstream.cpp:206-216), and callers ignore the error (stream.cpp:573-578). */
+ * (bitstream.cpp:206-216), and callers ignore the error (stream.cpp:573-578).
+ *
+ * The accepted bits go to the coder (a, o; the encoder and orc_serialize_slice)
+ * and / or into a record of the feed itself (orc_precode_slice, test
+ * infrastructure): LSB-first 32-bit words, the accepted bits of each of the
+ * eleven lists of the walk below, and the number of dropped writes. */
+enum { L_TYPES, L_TARGETS, L_MVX, L_MVY, L_SP_PRED, L_SP_AMOUNT, L_SP_INDEX, L_QUALITY, L_Y, L_U, L_V, L_COUNT };
+
 typedef struct {
     abac *a;
     obits *o;
     uint32_t w; /* write index since the last empty() */
+    /* the record (words may be NULL: counts only) */
+    int recording, list;
+    uint32_t *words;
+    uint64_t cap_words, total, dropped;
+    uint64_t list_bits[L_COUNT];
 } feed;
 
 static void feed_empty(feed *f) { f->w = 0; }
 static void feed_bits(feed *f, uint32_t value, uint32_t count) {
-    if (f->w + count > FEED_CAPACITY_BITS) return;
+    if (f->w + count > FEED_CAPACITY_BITS) {
+        f->dropped++;
+        return;
+    }
     f->w += count;
-    for (uint32_t k = 0; k < count; k++) abac_bit(f->a, (value >> k) & 1u, f->o);
+    for (uint32_t k = 0; k < count; k++) {
+        uint32_t b = (value >> k) & 1u;
+        if (f->a) abac_bit(f->a, b, f->o);
+        if (f->recording) {
+            if (f->words && (f->total >> 5) < f->cap_words) {
+                uint32_t *p = &f->words[f->total >> 5];
+                uint32_t s = (uint32_t)(f->total & 31);
+                *p = (*p & ~(1u << s)) | (b << s);
+            }
+            f->total++;
+        }
+    }
+    f->list_bits[f->list] += count;
 }
 
 /* encode_unsigned_golomb_value (golomb.cpp:8-58) / signed (golomb.cpp:21-84).
@@ -866,9 +893,17 @@ static void put_ue(feed *f, uint16_t v) {
     uint32_t code = golomb_from((uint32_t)v + 1, &n);
     feed_bits(f, code, n);
 }
+/* A coded value of -32768 is OUTSIDE THE REFERENCE'S DEFINED BEHAVIOUR: its
+ * abs is taken in int32 (32768), the mapped value 65537 has a 33-bit code, and
+ * golomb.cpp:63-91 hands 33 bits of a 4-byte variable to
+ * bit_stream::write_bits (bitstream.cpp:202).  The encoder cannot produce the
+ * value (no test stream holds it).  This project's rule, which
+ * the product's host and GPU precodes follow: |-32768| = 32767, so that -32768
+ * is coded as -32767 and every code has at most 31 bits. */
 static void put_se(feed *f, int16_t v) {
     uint32_t n;
-    uint32_t value = v == 0 ? 1u : (((uint32_t)iabs32(v) << 1) | (uint32_t)((v >> 15) & 1));
+    int32_t mag = v == INT16_MIN ? INT16_MAX : iabs32(v);
+    uint32_t value = v == 0 ? 1u : (((uint32_t)mag << 1) | (uint32_t)((v >> 15) & 1));
     uint32_t code = golomb_from(value, &n);
     feed_bits(f, code, n);
 }
@@ -923,69 +958,116 @@ static void ser_plane(feed *f, const int16_t *img, uint32_t width, uint32_t heig
         }
 }
 
-/* serialize_slice, serialize.cpp:319-340 (+ block table :125-317) */
-static void serialize_slice(const uint8_t *table, uint16_t count, int ring, const planes *coef,
-                            obits *o) {
-    abac a;
-    feed f = {&a, o, 0};
-    abac_clear(&a);
+/* serialize_slice's section walk, serialize.cpp:319-340 (+ block table
+ * :125-317), into a feed: the one walk behind the encoder's payload and the
+ * entry points on explicit inputs below. */
+static void slice_walk(const uint8_t *table, uint16_t count, int ring, const planes *coef, feed *f) {
     uint32_t tbits = lut_log2_u8((uint8_t)ring);
 
-    feed_empty(&f); /* serialize_block_types :125-135 */
-    for (uint32_t i = 0; i < count; i++) feed_bits(&f, tbl(table, i)->block_type & 7u, 3);
+    feed_empty(f); /* serialize_block_types :125-135 */
+    f->list = L_TYPES;
+    for (uint32_t i = 0; i < count; i++) feed_bits(f, tbl(table, i)->block_type & 7u, 3);
 
-    feed_empty(&f); /* serialize_prediction_targets :137-154 */
+    feed_empty(f); /* serialize_prediction_targets :137-154 */
+    f->list = L_TARGETS;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
         if (d->block_type & T_INTRA) continue;
-        feed_bits(&f, d->prediction_target & ((1u << tbits) - 1u), tbits);
+        feed_bits(f, d->prediction_target & ((1u << tbits) - 1u), tbits);
     }
 
-    feed_empty(&f); /* serialize_motion_vectors :156-191 */
+    feed_empty(f); /* serialize_motion_vectors :156-191 */
+    f->list = L_MVX;
     int16_t last = 0;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
         if (!(d->block_type & T_MOTION)) continue;
-        put_se(&f, (int16_t)(d->motion_x - last));
+        put_se(f, (int16_t)(d->motion_x - last));
         last = d->motion_x;
     }
+    f->list = L_MVY;
     last = 0;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
         if (!(d->block_type & T_MOTION)) continue;
-        put_se(&f, (int16_t)(d->motion_y - last));
+        put_se(f, (int16_t)(d->motion_y - last));
         last = d->motion_y;
     }
 
-    feed_empty(&f); /* serialize_subpixel_motion_params :193-241 */
+    feed_empty(f); /* serialize_subpixel_motion_params :193-241 */
+    f->list = L_SP_PRED;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
-        if (d->block_type & T_MOTION) feed_bits(&f, d->sp_pred & 1u, 1);
+        if (d->block_type & T_MOTION) feed_bits(f, d->sp_pred & 1u, 1);
     }
+    f->list = L_SP_AMOUNT;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
-        if ((d->block_type & T_MOTION) && d->sp_pred) feed_bits(&f, d->sp_amount & 1u, 1);
+        if ((d->block_type & T_MOTION) && d->sp_pred) feed_bits(f, d->sp_amount & 1u, 1);
     }
+    f->list = L_SP_INDEX;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
-        if ((d->block_type & T_MOTION) && d->sp_pred) feed_bits(&f, d->sp_index & 7u, 3);
+        if ((d->block_type & T_MOTION) && d->sp_pred) feed_bits(f, d->sp_index & 7u, 3);
     }
 
-    feed_empty(&f); /* serialize_block_quality :243-261 */
+    feed_empty(f); /* serialize_block_quality :243-261 */
+    f->list = L_QUALITY;
     int16_t lq = 0;
     for (uint32_t i = 0; i < count; i++) {
         const bdesc *d = tbl(table, i);
         if (d->block_type & T_COPY) continue;
-        put_se(&f, (int16_t)(d->q_index - lq));
+        put_se(f, (int16_t)(d->q_index - lq));
         lq = d->q_index;
     }
 
     /* serialize_macroblocks :125-155 */
-    ser_plane(&f, coef->y, (uint32_t)coef->w, (uint32_t)coef->h, 16, table);
-    ser_plane(&f, coef->u, (uint32_t)coef->w / 2, (uint32_t)coef->h / 2, 8, table);
-    ser_plane(&f, coef->v, (uint32_t)coef->w / 2, (uint32_t)coef->h / 2, 8, table);
+    f->list = L_Y;
+    ser_plane(f, coef->y, (uint32_t)coef->w, (uint32_t)coef->h, 16, table);
+    f->list = L_U;
+    ser_plane(f, coef->u, (uint32_t)coef->w / 2, (uint32_t)coef->h / 2, 8, table);
+    f->list = L_V;
+    ser_plane(f, coef->v, (uint32_t)coef->w / 2, (uint32_t)coef->h / 2, 8, table);
+}
 
+/* serialize_slice: the walk into the coder, then finish_encode. */
+static void serialize_slice(const uint8_t *table, uint16_t count, int ring, const planes *coef,
+                            obits *o) {
+    abac a;
+    feed f;
+    memset(&f, 0, sizeof(f));
+    f.a = &a;
+    f.o = o;
+    abac_clear(&a);
+    slice_walk(table, count, ring, coef, &f);
     abac_flush(&a, o); /* finish_encode */
+}
+
+/* The walk on explicit inputs (test infrastructure): a block table of
+ * wmb * hmb descs and coefficient planes of pitch wmb * 16 (chroma wmb * 8).
+ * orc_precode_slice records the accepted feed bits instead of coding them;
+ * orc_serialize_slice gives the payload serialize_slice makes of them. */
+uint64_t orc_precode_slice(const uint8_t *table, int wmb, int hmb, int ring, const int16_t *y,
+                           const int16_t *u, const int16_t *v, uint32_t *feed_words, uint64_t cap_words,
+                           uint64_t list_bits[11], uint64_t *dropped) {
+    planes coef = {(int16_t *)y, (int16_t *)u, (int16_t *)v, wmb * 16, hmb * 16};
+    feed f;
+    memset(&f, 0, sizeof(f));
+    f.recording = 1;
+    f.words = feed_words;
+    f.cap_words = feed_words ? cap_words : 0;
+    slice_walk(table, (uint16_t)(wmb * hmb), ring, &coef, &f);
+    if (list_bits) memcpy(list_bits, f.list_bits, sizeof(f.list_bits));
+    if (dropped) *dropped = f.dropped;
+    return f.total;
+}
+uint32_t orc_serialize_slice(const uint8_t *table, int wmb, int hmb, int ring, const int16_t *y,
+                             const int16_t *u, const int16_t *v, uint8_t *out, uint32_t cap_bits, int *err) {
+    planes coef = {(int16_t *)y, (int16_t *)u, (int16_t *)v, wmb * 16, hmb * 16};
+    obits o = {out, cap_bits, 0, 0};
+    serialize_slice(table, (uint16_t)(wmb * hmb), ring, &coef, &o);
+    if (err) *err = o.err;
+    return o.w;
 }
 
 /* ------------------------------------------------------------------ */

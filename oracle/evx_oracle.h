@@ -95,6 +95,27 @@ uint64_t orc_fnv1a64(uint64_t h, const uint8_t *data, uint64_t n);
 /* the arithmetic coder alone over a raw LSB-first feed (one slice + flush) */
 uint32_t orc_abac_feed(const uint32_t *words, uint64_t nbits, uint8_t *out, uint32_t cap_bits, int *err);
 
+/* serialize_slice's section walk (serialize.cpp:125-340) on explicit inputs:
+ * a block table of wmb * hmb descs (16 B each) and coefficient planes of pitch
+ * wmb * 16 (chroma wmb * 8) -- the walk orc_encode runs on its own state.
+ *
+ * orc_precode_slice records the feed bits the walk's bit stream accepts
+ * (bitstream.cpp:206-216: a write past the 32 Mbit of a section is dropped
+ * whole) instead of coding them: LSB first into feed_words (up to cap_words;
+ * NULL: counts only).  Returns the accepted bits in all; list_bits[11]: those
+ * of each list, in feed order (block types, prediction targets, motion x,
+ * motion y, sub-pel flag, amount, index, quality, then the Y, U and V
+ * coefficient sections); *dropped: the writes dropped.
+ * orc_serialize_slice: the ABAC payload of the same walk into out (LSB first)
+ * -> its bits; *err is set if they pass cap_bits.
+ * A coded value of -32768 is outside the reference's defined behaviour; it is
+ * coded as -32767 (evx_oracle.c put_se). */
+uint64_t orc_precode_slice(const uint8_t *table, int wmb, int hmb, int ring, const int16_t *y,
+                           const int16_t *u, const int16_t *v, uint32_t *feed_words, uint64_t cap_words,
+                           uint64_t list_bits[11], uint64_t *dropped);
+uint32_t orc_serialize_slice(const uint8_t *table, int wmb, int hmb, int ring, const int16_t *y,
+                             const int16_t *u, const int16_t *v, uint8_t *out, uint32_t cap_bits, int *err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,10 @@ def lib() -> ctypes.CDLL:
         L.orc_fnv1a64.argtypes = [ctypes.c_uint64, P, ctypes.c_uint64]
         L.orc_abac_feed.restype = U
         L.orc_abac_feed.argtypes = [P, ctypes.c_uint64, P, U, ctypes.POINTER(I)]
+        L.orc_precode_slice.restype = ctypes.c_uint64
+        L.orc_precode_slice.argtypes = [P, I, I, I, P, P, P, P, ctypes.c_uint64, P, P]
+        L.orc_serialize_slice.restype = U
+        L.orc_serialize_slice.argtypes = [P, I, I, I, P, P, P, P, U, ctypes.POINTER(I)]
         L.orc_transform_8x8.argtypes = [P, I, P, I]
         L.orc_sub_transform_8x8.argtypes = [P, I, P, I, P, I]
         L.orc_inverse_transform_8x8.argtypes = [P, I, P, I]
@@ -205,6 +209,48 @@ class OracleDecoder(OracleEncoder):
         st = self.L.orc_decode_frame(self.h, self.width, self.height, _ptr(t), _ptr(y), _ptr(u), _ptr(v))
         if st:
             raise RuntimeError(f"oracle decode failed: {st}")
+
+
+# The eleven lists of a slice's feed, in feed order (serialize.cpp:125-317).
+FEED_LISTS = ("types", "targets", "motion_x", "motion_y", "sp_pred", "sp_amount", "sp_index", "quality", "y", "u", "v")
+FEED_CAPACITY_BITS = 32 * 1024 * 1024  # per section (common.cpp:147)
+
+
+def _slice_inputs(table, wmb, hmb, y, u, v):
+    t = np.ascontiguousarray(table).view(np.uint8)
+    assert t.size == wmb * hmb * 16
+    y, u, v = (np.ascontiguousarray(a, dtype=np.int16) for a in (y, u, v))
+    assert y.shape == (hmb * 16, wmb * 16) and u.shape == v.shape == (hmb * 8, wmb * 8)
+    return t, y, u, v
+
+
+def precode_slice(table: np.ndarray, wmb: int, hmb: int, ring: int, y, u, v):
+    """The reference's section walk on explicit inputs, its accepted feed bits
+    recorded (orc_precode_slice) -> (words uint32 LSB first, bits, the bits of
+    each of the FEED_LISTS, dropped writes)."""
+    t, y, u, v = _slice_inputs(table, wmb, hmb, y, u, v)
+    lists = np.zeros(len(FEED_LISTS), np.uint64)
+    dropped = ctypes.c_uint64(0)
+    L = lib()
+    n = L.orc_precode_slice(_ptr(t), wmb, hmb, ring, _ptr(y), _ptr(u), _ptr(v), None, 0, _ptr(lists),
+                            ctypes.byref(dropped))
+    words = np.zeros((n + 31) // 32 + 1, np.uint32)
+    n2 = L.orc_precode_slice(_ptr(t), wmb, hmb, ring, _ptr(y), _ptr(u), _ptr(v), _ptr(words), words.size, _ptr(lists),
+                             ctypes.byref(dropped))
+    assert n2 == n
+    return words[: (n + 31) // 32], int(n), [int(x) for x in lists], int(dropped.value)
+
+
+def serialize_slice(table: np.ndarray, wmb: int, hmb: int, ring: int, y, u, v) -> tuple[bytes, int]:
+    """The ABAC payload of the same walk (orc_serialize_slice) -> (bytes, bits)."""
+    t, y, u, v = _slice_inputs(table, wmb, hmb, y, u, v)
+    cap = y.size * 56 + 65536  # a macroblock's codes stay below 6 * 1997 bits (47 per luma sample)
+    cap = min(cap, 0xFFFFFF00)
+    out = np.zeros(cap // 8 + 8, np.uint8)
+    err = ctypes.c_int(0)
+    n = lib().orc_serialize_slice(_ptr(t), wmb, hmb, ring, _ptr(y), _ptr(u), _ptr(v), _ptr(out), cap, ctypes.byref(err))
+    assert not err.value
+    return out[: (n + 7) // 8].tobytes(), int(n)
 
 
 def abac_feed(words: np.ndarray, nbits: int) -> tuple[bytes, int]:

@@ -31,14 +31,13 @@ def test_entropy_matches_oracle_odd_size(orc, cairo):
 
 def test_entropy_random_tables(orc, cairo):
     """Synthetic block tables/coefficients well outside natural statistics
-    (large coefficients, long runs, every type) against the oracle coder.
-    The oracle's entropy path is reached through a hand-built encoder state:
-    we compare the product with itself across two independent layouts and
-    with the oracle on natural data above; here we check determinism and the
-    exp-Golomb length law.  The host decode then has to recover them: every
-    field the stream carries and every coefficient (copy macroblocks carrying
-    zeros, as a first frame's do); tests/test_tables.py does the same over the
-    generator's sequences."""
+    (large coefficients, long runs, every type): the payload and the feed
+    equal the oracle's serialize_slice walk on the same inputs
+    (orc_serialize_slice, orc_precode_slice; tests/test_feed_tables.py does
+    the same over directed cases), and two calls on copies agree.  The host
+    decode then has to recover them: every field the stream carries and every
+    coefficient (copy macroblocks carrying zeros, as a first frame's do);
+    tests/test_tables.py does the same over the generator's sequences."""
     from tests.test_tables import carried, check_stream_fields
 
     rng = np.random.default_rng(7)
@@ -59,6 +58,11 @@ def test_entropy_random_tables(orc, cairo):
     a = cairo.serialize_slice(table, wmb, hmb, 4, y, u, v)
     b = cairo.serialize_slice(table.copy(), wmb, hmb, 4, y.copy(), u.copy(), v.copy())
     assert a == b and a[1] > 0
+    assert a == orc.serialize_slice(table, wmb, hmb, 4, y, u, v)
+    words, bits, lists, dropped = orc.precode_slice(table, wmb, hmb, 4, y, u, v)
+    got_words, got_bits = cairo.precode_slice(table, wmb, hmb, 4, y, u, v)
+    assert got_bits == bits == sum(lists) and dropped == 0
+    np.testing.assert_array_equal(got_words, words)
     want = carried(table, (y, u, v), None, wmb, hmb)
     pay, nb = cairo.serialize_slice(table, wmb, hmb, 4, *want)
     got, planes, used = cairo.unserialize_slice(pay, nb, wmb, hmb, 4)
