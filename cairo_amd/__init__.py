@@ -139,6 +139,16 @@ def lib() -> ctypes.CDLL:
         "cairo_kat_metrics": (I, [U, U, U, P, P, P, P, P, P, P, I]),
         "evx_encoder_set_metrics": (I, [P, I]),
         "evx_encoder_last_metrics": (I, [P, P]),
+        "cairo_rate_size": (I, []),
+        "cairo_rate_state_size": (I, []),
+        "cairo_rate_info_size": (I, []),
+        "cairo_rate_estimate": (ctypes.c_int64, [ctypes.c_uint64, ctypes.c_uint64]),
+        "cairo_rate_init": (I, [P, P]),
+        "cairo_rate_step": (I, [P, P, I, ctypes.c_int64, ctypes.POINTER(U)]),
+        "cairo_ctx_set_rate": (I, [P, P]),
+        "cairo_ctx_frame_rate": (I, [P, I, P]),
+        "cairo_stream_frame_rate": (I, [P, I, P]),
+        "cairo_kat_rate_observe": (I, [P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, P, I, P, I]),
         "cairo_ctx_wait": (I, [P, I, P]),
         "cairo_ctx_release": (I, [P, I]),
         "cairo_ctx_sync": (I, [P]),
@@ -695,6 +705,84 @@ def kat_metrics(a, b, w: int, h: int, device: int = 0) -> dict:
     return _metrics_dict(m)
 
 
+class _Rate(ctypes.Structure):
+    """cairo_rate (include/cairo_amd.h)."""
+    _fields_ = [("target_bits", ctypes.c_uint32), ("q0", ctypes.c_uint32), ("qmin", ctypes.c_uint32),
+                ("qmax", ctypes.c_uint32), ("window", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class _RateState(ctypes.Structure):
+    """cairo_rate_state."""
+    _fields_ = [("debt", ctypes.c_int64), ("p_aim", ctypes.c_int64), ("o_aim", ctypes.c_int64),
+                ("p_n", ctypes.c_int32), ("p_q", ctypes.c_int32), ("o_n", ctypes.c_int32), ("o_q", ctypes.c_int32),
+                ("launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class _RateInfo(ctypes.Structure):
+    """cairo_rate_info."""
+    _fields_ = [("quality", ctypes.c_uint32), ("overflow", ctypes.c_uint32), ("feed_bits", ctypes.c_uint64),
+                ("ones", ctypes.c_uint64), ("est_bits", ctypes.c_int64), ("aim", ctypes.c_int64),
+                ("debt", ctypes.c_int64)]
+
+
+RATE_FRAME_RECORD_BITS = 80  # a frame counts as its estimate plus its 10-byte frame record
+
+
+def _rate_dict(r: "_RateInfo") -> dict:
+    return {k: int(getattr(r, k)) for k, _ in _RateInfo._fields_}
+
+
+def rate_estimate(nbits: int, zeros: int) -> int:
+    """E(N, z): the integer estimate of the arithmetic coder's output, in bits,
+    for a feed of nbits bits of which zeros are 0 (cairo_rate_estimate)."""
+    e = lib().cairo_rate_estimate(nbits, zeros)
+    if e < 0:
+        raise ValueError(f"rate_estimate({nbits}, {zeros}): nbits must be below 2**32 and zeros at most nbits")
+    return int(e)
+
+
+class RateModel:
+    """The rate controller's law on the host (cairo_rate_init / cairo_rate_step):
+    what a Context with set_rate runs on the device.  step(n_new, obs_sum) ->
+    the quality of the next launch's n_new frames; obs_sum is the summed bits
+    (estimate + 80 each) of the frames of the launch before the last, read only
+    once two launches exist.  aim and debt are the state's after the step."""
+
+    def __init__(self, target_bits: int, q0: int = 8, qmin: int = 1, qmax: int = 31, window: int = 32):
+        self.cfg = _Rate(target_bits, q0, qmin, qmax, window)
+        self.state = _RateState()
+        _ck(lib().cairo_rate_init(ctypes.byref(self.state), ctypes.byref(self.cfg)), "cairo_rate_init")
+
+    def step(self, n_new: int, obs_sum: int = 0) -> int:
+        q = ctypes.c_uint32()
+        _ck(lib().cairo_rate_step(ctypes.byref(self.state), ctypes.byref(self.cfg), n_new, obs_sum, ctypes.byref(q)),
+            "cairo_rate_step")
+        return q.value
+
+    @property
+    def aim(self) -> int:
+        return int(self.state.p_aim)
+
+    @property
+    def debt(self) -> int:
+        return int(self.state.debt)
+
+
+def kat_rate_observe(words: np.ndarray, nbits, base: int = 0, stride: int | None = None, device: int = 0):
+    """The observing kernels on a host buffer, without a context
+    (cairo_kat_rate_observe): words (uint32) is uploaded whole, frame j's feed is
+    the nbits[j] bits from word base + j * stride on.  -> a list of dicts
+    (feed_bits, ones, est_bits, ...)."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    nb = np.ascontiguousarray(nbits, dtype=np.uint64)
+    if stride is None:
+        stride = int((int(nb.max()) + 31) // 32) if nb.size else 0
+    out = (_RateInfo * nb.size)()
+    _ck(lib().cairo_kat_rate_observe(_ptr(w), w.size, base, stride, _ptr(nb), nb.size, out, device),
+        "cairo_kat_rate_observe")
+    return [_rate_dict(r) for r in out]
+
+
 @dataclass
 class FrameOutputs:
     """Host copies of one frame's outputs (block table + output_cache)."""
@@ -706,6 +794,7 @@ class FrameOutputs:
     feed: np.ndarray | None = None  # OUT_FEED: the GPU precode's feed words (uint32, LSB-first)
     feed_bits: int = 0
     feed_status: int = 0  # FEED_NONE / FEED_VALID / FEED_OVERFLOW
+    quality: int = 0  # the quality the frame was coded with (with set_rate: the controller's choice)
 
 
 def _view(addr: int, dtype, count: int) -> np.ndarray:
@@ -879,12 +968,12 @@ class Context:
             _view(r.coef_y, np.int16, ny).reshape(r.ha, r.wa) if has_coef else None,
             _view(r.coef_u, np.int16, nc).reshape(r.ha // 2, r.wa // 2) if has_coef else None,
             _view(r.coef_v, np.int16, nc).reshape(r.ha // 2, r.wa // 2) if has_coef else None,
-            feed, int(r.feed_bits), int(r.feed_status),
+            feed, int(r.feed_bits), int(r.feed_status), int(r.quality),
         )
         if copy:
             cp = lambda a: None if a is None else a.copy()  # noqa: E731
             out = FrameOutputs(cp(out.table), cp(out.coef_y), cp(out.coef_u), cp(out.coef_v), cp(out.feed),
-                               out.feed_bits, out.feed_status)
+                               out.feed_bits, out.feed_status, out.quality)
         return out
 
     def set_outputs(self, outputs: int) -> None:
@@ -908,6 +997,26 @@ class Context:
         if flags is None:
             flags = (METRIC_SSE if sse else 0) | (METRIC_SSIM if ssim else 0) | (KEEP_RECON if keep_recon else 0)
         _ck(self.L.cairo_ctx_set_metrics(self.h, flags), "cairo_ctx_set_metrics")
+
+    def set_rate(self, target_bits: int | None, q0: int = 8, qmin: int = 1, qmax: int = 31, window: int = 32) -> None:
+        """Target bitrate (cairo_ctx_set_rate): from now on the context chooses
+        one quality per launch on the device so that frames average target_bits
+        (payload plus the 10-byte frame record); the quality of a submit is
+        ignored, FrameOutputs.quality and frame_rate report the choice.
+        window: frames over which a debt is paid back.  None turns it off.  No
+        frame may be in flight; the outputs must include OUT_FEED."""
+        if target_bits is None:
+            _ck(self.L.cairo_ctx_set_rate(self.h, None), "cairo_ctx_set_rate")
+            return
+        cfg = _Rate(target_bits, q0, qmin, qmax, window)
+        _ck(self.L.cairo_ctx_set_rate(self.h, ctypes.byref(cfg)), "cairo_ctx_set_rate")
+
+    def frame_rate(self, ticket: int) -> dict:
+        """What the rate controller saw and chose for a waited, unreleased
+        frame: quality, overflow, feed_bits, ones, est_bits, aim, debt."""
+        r = _RateInfo()
+        _ck(self.L.cairo_ctx_frame_rate(self.h, ticket, ctypes.byref(r)), "cairo_ctx_frame_rate")
+        return _rate_dict(r)
 
     def set_input_color(self, range: int, matrix: int) -> None:
         """The colour description (RANGE_*, MATRIX_*) of the I420 / NV12 frames
@@ -1388,6 +1497,14 @@ class Stream:
         m = _FrameMetrics()
         _ck(self.L.cairo_stream_frame_metrics(self.h, ticket, ctypes.byref(m)), "cairo_stream_frame_metrics")
         return _metrics_dict(m)
+
+    def frame_rate(self, ticket: int) -> dict:
+        """Context.frame_rate of a frame whose outputs the pipeline has picked
+        up (as frame_metrics); the frame record is the caller's to write, with
+        this quality."""
+        r = _RateInfo()
+        _ck(self.L.cairo_stream_frame_rate(self.h, ticket, ctypes.byref(r)), "cairo_stream_frame_rate")
+        return _rate_dict(r)
 
     def timeline(self, ticket: int):
         """(submitted, outputs on host, entropy start, entropy end, collected), us."""

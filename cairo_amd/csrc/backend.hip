@@ -36,6 +36,7 @@
 #include "kernels.h"
 #include "metrics.h"
 #include "precode.h"
+#include "rate_kernels.h"
 #include "scale.h"
 #include "tensor.h"
 
@@ -92,6 +93,7 @@ struct Stage {
   bool launched = false;  // its batch has been launched
   bool waited = false;    // its outputs were handed to a caller (cairo_ctx_wait)
   int mflags = 0;         // cairo_ctx_set_metrics flags in force at its submit (0 for a decoded frame)
+  bool rated = false;     // cairo_ctx_set_rate was on at its submit: its launch's quality is the controller's
   uint32_t index = 0, type = 0, quality = 0;
 };
 
@@ -99,6 +101,7 @@ struct Stage {
 void take_stage(Stage& s, int t, uint32_t index, uint32_t type, uint32_t quality, int mflags) {
   s.busy = true, s.launched = false, s.waited = false;
   s.mflags = mflags;
+  s.rated = false;
   s.ticket = t;
   s.index = index, s.type = type, s.quality = quality;
 }
@@ -275,6 +278,20 @@ struct cairo_ctx {
   MetricsPartial* met_part = nullptr;  // [stages][3][metrics_tiles(w, h)]
   cairo_frame_metrics* met_host = nullptr;  // [stages]
   cairo_frame_metrics* met_dev = nullptr;   // its device-visible address
+  // Target bitrate (cairo_ctx_set_rate): the controller's state
+  // lives on the device; launch L's k_rate_decide reads what launch L-2's
+  // k_rate_observe wrote, by stream order (the launches alternate between two
+  // streams).  The host only keeps which slots the last two launches used.
+  bool rate_on = false;
+  cairo_rate rate_cfg = {};
+  cairo_rate_state* rate_state = nullptr;  // device
+  RateSlot* rate_dev = nullptr;            // [stages]
+  uint32_t* rate_part = nullptr;           // [stages][kRateBlocks]
+  RateSlot* rate_host = nullptr;           // mapped pinned [stages]
+  RateSlot* rate_host_dev = nullptr;       // its device-visible address
+  int rate_launches = 0;                   // launches since the controller (re)started, up to 2
+  int rate_n[2] = {};                      // frames of the last launch [0] and of the one before [1]
+  int rate_slot[2][kMaxBatch] = {};        // and their staging slots
   // Thread safety (the frame pipeline of pipeline.cpp calls in from its
   // completion and entropy threads): every public entry point holds mu;
   // HIP event waits on a frame's outputs run outside it.  launched_cv is
@@ -486,12 +503,14 @@ void free_ctx(cairo_ctx* c) {
   if (c->fs) (void)hipStreamDestroy(c->fs);
   if (c->trace_host) (void)hipHostFree(c->trace_host);
   if (c->met_host) (void)hipHostFree(c->met_host);
+  if (c->rate_host) (void)hipHostFree(c->rate_host);
   leave_group(c);
   for (int16_t* q : c->coef)
     if (q) (void)hipFree(q);
   for (void* p : {(void*)c->fdesc, (void*)c->order, (void*)c->src, (void*)c->table, (void*)c->idesc, (void*)c->progress, (void*)c->feed_dev, (void*)c->feed_hdr, (void*)c->feed_scratch,
                   (void*)c->gran, (void*)c->rgb, (void*)c->ring_buf, (void*)c->sync, (void*)c->sticky,
-                  (void*)c->predeblock, (void*)c->stamps, (void*)c->acct, (void*)c->keep, (void*)c->met_part})
+                  (void*)c->predeblock, (void*)c->stamps, (void*)c->acct, (void*)c->keep, (void*)c->met_part,
+                  (void*)c->rate_state, (void*)c->rate_dev, (void*)c->rate_part})
     (void)hipFree(p);
   if (c->us) (void)hipStreamSynchronize(c->us);
   if (c->up_last) (void)hipEventDestroy(c->up_last);
@@ -790,6 +809,25 @@ int enqueue_convert(cairo_ctx* c, Launch& l) {
       s.rgb_pending = true;
     }
   }
+  // Target bitrate: the launch's quality goes into its views here, after the
+  // convert kernel that writes them and before batch_ready is recorded -- the
+  // next launch's workers may run this launch's tasks from these views as soon
+  // as that event fires.  It reads the records of launch b-2, which precedes
+  // this one on the same stream, k_rate_observe included.
+  if (c->rate_on) {
+    RateDecideArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.cfg = c->rate_cfg;
+    ra.state = c->rate_state;
+    ra.obs = c->rate_dev;
+    ra.host = c->rate_host_dev;
+    ra.fa = l.fd;
+    ra.n_new = e.nframes;
+    ra.n_obs = c->rate_launches >= 2 ? c->rate_n[1] : 0;
+    for (int i = 0; i < ra.n_obs; i++) ra.oslot[i] = c->rate_slot[1][i];
+    for (int i = 0; i < e.nframes; i++) ra.nslot[i] = c->pend[i].f.slot;
+    CK(launch_rate_decide(ra, st));
+  }
   CK(hipEventRecord(c->batch_ready[l.area], st));
   // the previous batch's tasks, which this launch's workers may run, need its
   // frames converted and its views and sync area in place
@@ -875,6 +913,23 @@ int enqueue_results(cairo_ctx* c, Launch& l) {
   }
   fa.table_words = (int)(c->mbs * sizeof(BlockDesc) / sizeof(uint4));
   CK(launch_precode(fa, (int)c->mbs, st));
+  // Target bitrate: the frames' set bits are counted right behind the precode
+  // on the launch's stream, before pre_done is recorded: ahead of every
+  // frame's d2h_done (the host reads the slot's record after it) and of the
+  // launch two ahead on this stream, whose k_rate_decide reads it.
+  if (c->rate_on) {
+    RateObserveArgs ro;
+    memset(&ro, 0, sizeof(ro));
+    ro.nframes = e.nframes;
+    for (int i = 0; i < e.nframes; i++) ro.slot[i] = fa.slot[i];
+    ro.feed = c->feed_dev;
+    ro.feed_stride = c->feed_words;
+    ro.hdr = c->feed_hdr;
+    ro.part = c->rate_part;
+    ro.dev = c->rate_dev;
+    ro.host = c->rate_host_dev;
+    CK(launch_rate_observe(ro, st));
+  }
   // The copy into the mapped host stages is PCIe-bound and no engine
   // launch needs it: on the copy stream, so that the launch two ahead on
   // this stream starts without it (+0.2 %, profiles/r06/ab_4k_feed_copy_aside.txt).
@@ -949,6 +1004,13 @@ int flush(cairo_ctx* c) {
   if (!r) r = enqueue_results(c, l);
   if (!r) r = enqueue_copies(c, l);
   if (r) return r;
+  if (c->rate_on) {  // the launch before the last is the one the next launch observes
+    c->rate_n[1] = c->rate_n[0];
+    memcpy(c->rate_slot[1], c->rate_slot[0], sizeof(c->rate_slot[0]));
+    c->rate_n[0] = c->npend;
+    for (int i = 0; i < c->npend; i++) c->rate_slot[0][i] = c->pend[i].f.slot;
+    if (c->rate_launches < 2) c->rate_launches++;
+  }
   c->last_slot = c->pend[c->npend - 1].f.slot;
   c->last_epoch = c->pend[c->npend - 1].f.epoch;
   c->npend = 0;
@@ -1127,6 +1189,17 @@ int write_staged(const cairo_ctx* c, int slot, const FrameSink& out, hipStream_t
   return copy_frame(c, staged, out.base, false, out.fmt, out.pitch, st);
 }
 
+// A fresh controller state on the device (nothing is in flight), and no launch
+// to observe yet.
+int restart_rate(cairo_ctx* c) {
+  cairo_rate_state s;
+  rate_init(&s);
+  CK(hipMemcpy(c->rate_state, &s, sizeof(s), hipMemcpyHostToDevice));
+  c->rate_launches = 0;
+  c->rate_n[0] = c->rate_n[1] = 0;
+  return kSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1252,7 +1325,9 @@ int cairo_ctx_reset(cairo_ctx* c) {
     r = upload_orders(c, kOrderSlope);
     if (r) return r;
   }
-  return zero_state(c);
+  r = zero_state(c);
+  if (r == kSuccess && c->rate_on) r = restart_rate(c);  // the controller starts over at q0
+  return r;
 }
 
 int cairo_ctx_stages(const cairo_ctx* c) { return c ? c->stages : 0; }
@@ -1491,10 +1566,12 @@ static int frame_result(cairo_ctx* c, Stage& s, cairo_frame_result* out, bool po
   out->hmb = c->hmb;
   out->index = s.index;
   out->type = s.type;
+  // the controller's choice: k_rate_decide wrote it before the frame's d2h_done
+  if (s.rated) s.quality = ((const volatile RateSlot*)c->rate_host)[&s - c->st.data()].quality;
   out->quality = s.quality;
-  if (s.mflags) {  // (set at its submit, under mu, before this frame could be waited on)
+  if (s.mflags || s.rated) {  // (set at its submit, under mu, before this frame could be waited on)
     std::lock_guard<std::mutex> lk(c->mu);
-    s.waited = true;  // cairo_ctx_frame_metrics / fetch_recon may be used now
+    s.waited = true;  // cairo_ctx_frame_metrics / fetch_recon / frame_rate may be used now
   }
   return kSuccess;
 }
@@ -1552,6 +1629,7 @@ int cairo_ctx_timeout_info(cairo_ctx* c, int32_t* out, int n) {
 int cairo_ctx_set_outputs(cairo_ctx* c, int outputs) {
   if (!c || outputs < 1 || outputs > (CAIRO_OUT_COEF | CAIRO_OUT_FEED)) return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
+  if (c->rate_on && !(outputs & CAIRO_OUT_FEED)) return kInvalidArg;  // the controller observes the feed
   CK(hipSetDevice(c->device));
   int r = sync_all(c);  // frames in flight keep the outputs they were launched with
   if (r) return r;
@@ -1661,6 +1739,65 @@ int cairo_ctx_frame_metrics(cairo_ctx* c, int ticket, cairo_frame_metrics* out) 
   if (!s || !(s->mflags & (CAIRO_METRIC_SSE | CAIRO_METRIC_SSIM))) return kInvalidArg;
   // written by k_metrics_finish before the frame's d2h_done, which its wait saw
   memcpy(out, (const void*)(c->met_host + ticket % c->stages), sizeof(*out));
+  return kSuccess;
+}
+
+int cairo_ctx_set_rate(cairo_ctx* c, const cairo_rate* cfg) {
+  if (!c) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  // a refused call changes nothing: no flush before the checks (a pending
+  // frame's stage is busy, so nothing is pending once they pass)
+  if (cfg && (!rate_cfg_ok(cfg) || !(c->outputs & CAIRO_OUT_FEED) || c->gsize > 1)) return kInvalidArg;
+  for (const Stage& s : c->st)
+    if (s.busy) return kInvalidResource;
+  CK(hipSetDevice(c->device));
+  int r = sync_all(c);  // released, unwaited frames may still run
+  if (r) return r;
+  if (!cfg) {
+    c->rate_on = false;  // the buffers stay until the context goes
+    return kSuccess;
+  }
+  if (!c->rate_host) {  // all or nothing
+    const size_t S = (size_t)c->stages;
+    cairo_rate_state* state = nullptr;
+    RateSlot *dev = nullptr, *host = nullptr, *host_dev = nullptr;
+    uint32_t* part = nullptr;
+    hipError_t e = hipMalloc(&state, sizeof(cairo_rate_state));
+    if (e == hipSuccess) e = hipMalloc(&dev, sizeof(RateSlot) * S);
+    if (e == hipSuccess) e = hipMalloc(&part, sizeof(uint32_t) * kRateBlocks * S);
+    if (e == hipSuccess) e = hipHostMalloc(&host, sizeof(RateSlot) * S, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&host_dev, host, 0);
+    if (e == hipSuccess) e = hipMemset(dev, 0, sizeof(RateSlot) * S);
+    if (e != hipSuccess) {
+      for (void* q : {(void*)state, (void*)dev, (void*)part}) (void)hipFree(q);
+      if (host) (void)hipHostFree(host);
+      return fail(e, "set_rate: controller buffers");
+    }
+    memset(host, 0, sizeof(RateSlot) * S);
+    c->rate_state = state, c->rate_dev = dev, c->rate_part = part, c->rate_host = host, c->rate_host_dev = host_dev;
+  }
+  r = restart_rate(c);
+  if (r) return r;
+  c->rate_cfg = *cfg;
+  c->rate_on = true;
+  return kSuccess;
+}
+
+int cairo_ctx_frame_rate(cairo_ctx* c, int ticket, cairo_rate_info* info) {
+  if (!c || !info || ticket < 0) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(c->mu);
+  const Stage& s = c->st[ticket % c->stages];
+  if (s.ticket != ticket || !s.busy || !s.waited || !s.rated || !c->rate_host) return kInvalidArg;
+  // written by k_rate_decide and k_rate_finish before the frame's d2h_done, which its wait saw
+  RateSlot r;
+  memcpy(&r, (const void*)(c->rate_host + ticket % c->stages), sizeof(r));
+  info->quality = r.quality;
+  info->overflow = r.overflow;
+  info->feed_bits = r.nbits;
+  info->ones = r.ones;
+  info->est_bits = rate_frame_bits(r.nbits, r.ones, r.overflow, c->rate_cfg.target_bits);
+  info->aim = r.aim;
+  info->debt = r.debt;
   return kSuccess;
 }
 
@@ -1847,6 +1984,7 @@ int cairo_ctx_join_group(cairo_ctx* c, int size, int rank, const cairo_peer* pee
   std::lock_guard<std::mutex> lk(c->mu);
   if (!c->fresh || c->npend || c->gsize > 1) return kInvalidResource;
   if (c->metrics) return kInvalidArg;  // a member's deblock pushes to its mirrors, not to a keep
+  if (c->rate_on) return kInvalidArg;  // the controller sees one context's launches, not the stream's
   CK(hipSetDevice(c->device));
   if (size == 1) return kSuccess;
   const pid_t me = getpid();
@@ -2237,6 +2375,7 @@ int submit_frame(cairo_ctx* c, const FrameSource& src, uint32_t index, uint32_t 
   frame_links(c, f, t);
   c->npend++;
   take_stage(s, t, index, type, quality, c->metrics);
+  s.rated = c->rate_on;
   c->next_ticket++;
   *ticket = t;
   if (c->npend >= c->batch_max) return flush(c);
@@ -2254,6 +2393,7 @@ int decode_frame(cairo_ctx* c, const uint8_t* table, const int16_t* coef, uint32
     return kInvalidArg;
   std::lock_guard<std::mutex> lk(c->mu);
   if (c->gsize > 1) return kInvalidResource;
+  if (c->rate_on) return kInvalidResource;  // a decode launch between two encode launches has no feed to observe
   CK(hipSetDevice(c->device));
   if (out.tensor && !device_span(c, out.base, span, "decode_frame_tensor")) return kInvalidArg;
   int r = flush(c);  // encode frames still pending go first, in their own launch

@@ -60,6 +60,8 @@ struct Frame {
   uint64_t nbits = 0;
   bool has_metrics = false;  // cairo_ctx_set_metrics was on for the frame
   cairo_frame_metrics metrics = {};
+  bool has_rate = false;  // cairo_ctx_set_rate was on for the frame
+  cairo_rate_info rate = {};
 };
 
 struct Job {
@@ -116,12 +118,16 @@ struct cairo_stream {
       // the frame's metrics, while its ticket is unreleased (none: metrics off)
       cairo_frame_metrics fm;
       const bool has = cairo_ctx_frame_metrics(ctx, t, &fm) == kSuccess;
+      cairo_rate_info ri;  // and what the rate controller chose for it (none: off)
+      const bool rated = cairo_ctx_frame_rate(ctx, t, &ri) == kSuccess;
       {
         std::lock_guard<std::mutex> lk(m);
         Frame& f = at(t);
         f.t[kTOutputs] = now_us();
         f.has_metrics = has;
         if (has) f.metrics = fm;
+        f.has_rate = rated;
+        if (rated) f.rate = ri;
         jobs.push_back(j);
       }
       cv.notify_all();
@@ -267,6 +273,7 @@ static int stream_submit(cairo_stream* s, const cairo::FrameSource& src, uint32_
     f.status = kSuccess;
     f.nbits = 0;
     f.has_metrics = false;
+    f.has_rate = false;
     s->todo.push_back(tk);
   }
   s->cv.notify_all();
@@ -379,6 +386,15 @@ int cairo_stream_frame_metrics(cairo_stream* s, int ticket, cairo_frame_metrics*
   const Frame& f = s->at(ticket);
   if (f.ticket != ticket || f.state == Frame::kSubmitted || !f.has_metrics) return kInvalidArg;
   *out = f.metrics;
+  return kSuccess;
+}
+
+int cairo_stream_frame_rate(cairo_stream* s, int ticket, cairo_rate_info* out) {
+  if (!s || !out || ticket < 0) return kInvalidArg;
+  std::lock_guard<std::mutex> lk(s->m);
+  const Frame& f = s->at(ticket);
+  if (f.ticket != ticket || f.state == Frame::kSubmitted || !f.has_rate) return kInvalidArg;
+  *out = f.rate;
   return kSuccess;
 }
 

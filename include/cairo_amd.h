@@ -73,7 +73,13 @@ extern "C" {
  *      cairo_stream_submit_tensor_scaled, cairo_kat_tensor_scale.
  *   4  (unchanged) cairo_kat_precode is added.  The host precode codes a value
  *      of -32768 as -32767 (31 bits, as the GPU precode always did) where it
- *      used to write 32 bits of a 33-bit code; no encoder produces the value. */
+ *      used to write 32 bits of a 33-bit code; no encoder produces the value.
+ *   4  (unchanged) the target bitrate adds entry points only: cairo_rate_size,
+ *      cairo_rate_state_size, cairo_rate_info_size, cairo_rate_estimate,
+ *      cairo_rate_init, cairo_rate_step, cairo_ctx_set_rate,
+ *      cairo_ctx_frame_rate, cairo_stream_frame_rate, cairo_kat_rate_observe.
+ *      A context on which cairo_ctx_set_rate was never called behaves as
+ *      before. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -758,6 +764,103 @@ CAIRO_API int cairo_kat_metrics(uint32_t w, uint32_t h, uint32_t pitch_elems, co
                                 const int16_t *b_u, const int16_t *b_v, cairo_frame_metrics *out,
                                 int device);
 
+/* ---- target bitrate ---------------------------------------
+ * With a cairo_rate set, the context chooses one quality per launch on the
+ * device, from the sizes of the frames of earlier launches; the host is not in
+ * the loop.  A frame's size is known on the device from its feed alone: the
+ * arithmetic coder's adaptive model keeps plain counts, so its output for a
+ * feed of N bits with z zeros is log2((N+1)! / (z! (N-z)!)) bits within its
+ * termination, whatever their order.  The integer estimate of that is
+ *
+ *   L(x), 1 <= x < 2^32, Q16:  e = 31 - clz(x);  y = x << (31 - e);  sixteen
+ *     times: y = (y * y) >> 31 (64-bit product), append bit (y >= 2^32), and if
+ *     that bit is set y >>= 1;  L = (e << 16) | the sixteen bits
+ *   E(N, z) = (N L(N) - z L(z) - (N-z) L(N-z)) >> 16   (a term with a zero
+ *     factor is 0; N < 2^32, z <= N)
+ *
+ * and a frame counts as E + 80 bits (its 10-byte frame record; the stream
+ * header is not counted), or 4 * target_bits when its feed overflowed.
+ *
+ * The control law is a pure function on cairo_rate_state.  P is the last
+ * launch, O the one before, each {n frames, quality q, aim}; T = target_bits,
+ * W = window.  step(n_new, obs_sum), obs_sum the summed bits of O's frames:
+ *   fewer than two launches so far:  q = q0, aim = T
+ *   otherwise:
+ *     debt += obs_sum - O.n T                        (kept within +-2^60)
+ *     Dp  = debt + P.n (P.aim - T)
+ *     aim = clamp(T - Dp / W, max(T / 4, 1), 4 T)    (division toward zero)
+ *     M = obs_sum / O.n;  s = max(0, bitlen(max(M, aim)) - 24)
+ *     m = M >> s;  t = max(aim >> s, 1)
+ *     qm = (O.q m^2 + t^2 / 2) / t^2                 (uint64)
+ *     st = 1 + P.q / 4
+ *     q = clamp(qm, P.q - st, P.q + st)
+ *   q = clamp(q, qmin, qmax);  O = P;  P = {n_new, q, aim} */
+typedef struct cairo_rate {
+  uint32_t target_bits;  /* T, per frame: 1 .. 2^28 */
+  uint32_t q0;           /* the quality of the first two launches, 1..31 */
+  uint32_t qmin, qmax;   /* 1 <= qmin <= qmax <= 31 */
+  uint32_t window;       /* W >= 1: frames over which a debt is paid back */
+  uint32_t reserved[3];  /* 0 */
+} cairo_rate;
+typedef struct cairo_rate_state {
+  int64_t debt;          /* observed bits minus T per observed frame */
+  int64_t p_aim, o_aim;
+  int32_t p_n, p_q, o_n, o_q;
+  uint32_t launches;
+  uint32_t reserved;
+} cairo_rate_state;
+typedef struct cairo_rate_info {
+  uint32_t quality;      /* the quality the frame was coded with */
+  uint32_t overflow;     /* its feed overflowed (feed_bits and ones are 0) */
+  uint64_t feed_bits;    /* N */
+  uint64_t ones;         /* set bits among them */
+  int64_t est_bits;      /* E(N, N - ones) + 80; 4 T on overflow */
+  int64_t aim;           /* bits per frame its launch aimed at */
+  int64_t debt;          /* the state's debt after its launch's step */
+} cairo_rate_info;
+/* sizeof of the three, for bindings. */
+CAIRO_API int cairo_rate_size(void);
+CAIRO_API int cairo_rate_state_size(void);
+CAIRO_API int cairo_rate_info_size(void);
+/* Host only, no device needed.  E(N, zeros); -1 for N >= 2^32 or zeros > N. */
+CAIRO_API int64_t cairo_rate_estimate(uint64_t nbits, uint64_t zeros);
+/* A fresh state for cfg; EVX_ERROR_INVALID_ARGS for a bad configuration
+ * (a field out of the ranges above, a reserved word set). */
+CAIRO_API int cairo_rate_init(cairo_rate_state *state, const cairo_rate *cfg);
+/* One step of the law: *q is the quality of the next launch's n_new frames
+ * (1 .. 65535), obs_sum (0 .. 2^48) as above.  EVX_ERROR_INVALID_ARGS leaves
+ * the state as it was. */
+CAIRO_API int cairo_rate_step(cairo_rate_state *state, const cairo_rate *cfg, int n_new, int64_t obs_sum,
+                              uint32_t *q);
+/* Turn the controller on (a fresh state for cfg) or, with cfg NULL, off.
+ * EVX_ERROR_INVALID_RESOURCE with a frame in flight (submitted and not
+ * released); EVX_ERROR_INVALID_ARGS for a bad configuration, for a context
+ * whose outputs do not include CAIRO_OUT_FEED, and for a member of a group.  A
+ * refused call changes nothing.  While it is on: every launch is preceded by
+ * one step, whose quality all its frames are coded with (the quality of a
+ * submit is still validated, and otherwise unused); cairo_frame_result.quality
+ * reports the chosen value; cairo_ctx_reset restarts the controller;
+ * cairo_ctx_join_group (EVX_ERROR_INVALID_ARGS), cairo_ctx_set_outputs without
+ * CAIRO_OUT_FEED (EVX_ERROR_INVALID_ARGS) and cairo_ctx_decode_frame*
+ * (EVX_ERROR_INVALID_RESOURCE) are refused.  Launch L is stepped with the
+ * frames of launch L-2, by stream order alone: for one sequence of calls
+ * (submits, batch size, flushes, waits of unlaunched frames) the qualities are
+ * always the same.  While it is off, a launch is what it is without this
+ * call. */
+CAIRO_API int cairo_ctx_set_rate(cairo_ctx *ctx, const cairo_rate *cfg);
+/* What the controller saw and chose for a waited, unreleased frame that was
+ * submitted while it was on; EVX_ERROR_INVALID_ARGS otherwise. */
+CAIRO_API int cairo_ctx_frame_rate(cairo_ctx *ctx, int ticket, cairo_rate_info *info);
+/* Known-answer check of the observing kernels on host buffers, without a
+ * context or the engine: `total_words` words are uploaded whole, frame j's
+ * feed is the nbits[j] bits from word base_words + j * stride_words on (it
+ * must lie inside the buffer; count 1..48).  Bits beyond nbits[j] may be set:
+ * they are not counted.  Out, per frame: feed_bits, ones and est_bits (the
+ * other fields 0). */
+CAIRO_API int cairo_kat_rate_observe(const uint32_t *words, uint64_t total_words, uint64_t base_words,
+                                     uint64_t stride_words, const uint64_t *nbits, int count,
+                                     cairo_rate_info *out, int device);
+
 /* Known-answer check of the device transform chain: count macroblocks of 384
  * int16 (block-major: Y TL,TR,BL,BR, U, V; 64 each).  qtype[2m] = block type,
  * qtype[2m+1] = frame quality.  Host buffers in and out. */
@@ -908,6 +1011,11 @@ CAIRO_API int cairo_stream_timeline(cairo_stream *s, int ticket, double *t);
  * frame's outputs, valid for a collected frame until ticket + 2*stages is
  * submitted.  EVX_ERROR_INVALID_ARGS when the frame has none. */
 CAIRO_API int cairo_stream_frame_metrics(cairo_stream *s, int ticket, cairo_frame_metrics *out);
+/* The same for cairo_ctx_frame_rate, of a context with cairo_ctx_set_rate on
+ * (turned on while the stream has no frame in flight; the stream's context
+ * has CAIRO_OUT_FEED).  The frame record of the frame (quality included) is
+ * the caller's to write: take the quality from here. */
+CAIRO_API int cairo_stream_frame_rate(cairo_stream *s, int ticket, cairo_rate_info *out);
 /* Finish all submitted frames and stop the threads. */
 CAIRO_API int cairo_stream_destroy(cairo_stream *s);
 /* Append n bits of src at bit *pos of dst (cap_bits), bit_stream semantics. */
