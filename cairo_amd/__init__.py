@@ -178,6 +178,7 @@ def lib() -> ctypes.CDLL:
         "cairo_task_order": (I, [I, I, P, ctypes.POINTER(I)]),
         "cairo_task_queues": (I, [I, I, I, I, I, P, P, ctypes.POINTER(I)]),
         "cairo_kat_transform": (I, [P, P, P, I, P, P, P, I]),
+        "cairo_kat_quant": (I, [P, P, I, P, P, I]),
         "cairo_kat_precode": (I, [U, U, U, I, I, P, P, P, P, P, U, P, P, ctypes.c_uint64, P, U, I]),
         "cairo_serialize_slice": (I, [P, U, U, U, P, P, P, P, U, ctypes.POINTER(U)]),
         "cairo_serialize_feed": (I, [P, ctypes.c_uint64, P, U, ctypes.POINTER(U)]),
@@ -1398,6 +1399,20 @@ def kat_precode(frames, wmb: int, hmb: int, ring: int, slots=None, nslots: int |
                                 prefill, _ptr(hdr), _ptr(feed) if feed_words else None, feed_words,
                                 _ptr(guard) if guard_words else None, guard_words, device), "cairo_kat_precode")
     return hdr, feed, guard
+
+
+def kat_quant(coef: np.ndarray, types, qps, device: int = 0):
+    """The device quantizer and dequantizer alone (cairo_kat_quant): coef is
+    (n, 384) int16 in kat_transform's layout, types[m] the block type (0..3)
+    and qps[m] the qp itself (1..31) of macroblock m -> (quant, dequant), both
+    (n, 384) int16."""
+    coef = np.ascontiguousarray(coef, dtype=np.int16).reshape(-1, 384)
+    n = coef.shape[0]
+    tq = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(types, np.uint8), (n,)),
+                                        np.broadcast_to(np.asarray(qps, np.uint8), (n,))], 1))
+    quant, dequant = np.zeros_like(coef), np.zeros_like(coef)
+    _ck(lib().cairo_kat_quant(_ptr(coef), _ptr(tq), n, _ptr(quant), _ptr(dequant), device), "cairo_kat_quant")
+    return quant, dequant
 
 
 def unserialize_slice(payload: bytes, nbits: int, wmb: int, hmb: int, ring: int, table=None, planes=None,

@@ -2203,6 +2203,25 @@ int cairo_kat_transform(const int16_t* src, const int16_t* pred, const uint8_t* 
   return kSuccess;
 }
 
+int cairo_kat_quant(const int16_t* coef, const uint8_t* tq, int count, int16_t* quant, int16_t* dequant,
+                    int device) {
+  if (!coef || !tq || !quant || !dequant || count < 1) return kInvalidArg;
+  for (int m = 0; m < count; m++)
+    if ((tq[2 * m] & kCopy) || tq[2 * m + 1] < 1 || tq[2 * m + 1] > 31) return kInvalidArg;
+  CK(hipSetDevice(device));
+  const size_t n = (size_t)count * 384;
+  KatBuffer dc, dt, dq, dd;
+  int r;
+  if ((r = dc.alloc(n * 2)) || (r = dt.alloc((size_t)count * 2)) || (r = dq.alloc(n * 2)) || (r = dd.alloc(n * 2)) ||
+      (r = dc.upload(coef, n * 2)) || (r = dt.upload(tq, (size_t)count * 2)) ||
+      (r = kat_run(launch_kat_quant(dc.as<int16_t>(), dt.as<uint8_t>(), dq.as<int16_t>(), dd.as<int16_t>(), count,
+                                    nullptr),
+                   "kat_quant")) ||
+      (r = dq.download(quant, n * 2)) || (r = dd.download(dequant, n * 2)))
+    return r;
+  return kSuccess;
+}
+
 int cairo_kat_precode(uint32_t wmb, uint32_t hmb, uint32_t ring, int count, int nslots, const int32_t* slot,
                       const uint8_t* tables, const int16_t* coef_y, const int16_t* coef_u, const int16_t* coef_v,
                       uint32_t prefill, uint32_t* hdr, uint32_t* feed, uint64_t feed_words, uint32_t* guard,

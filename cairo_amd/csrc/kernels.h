@@ -496,5 +496,8 @@ hipError_t launch_yuv_to_rgb(PlaneSet src, int wa, int w, int h, uint8_t* rgb, h
 hipError_t launch_kat_transform(const int16_t* src, const int16_t* pred, int16_t* coef,
                                 int16_t* recon, const uint8_t* qtype, int32_t* qvar,
                                 int count, hipStream_t s);
+// The quantizer and dequantizer alone: tq[2m] = block type, tq[2m+1] = qp.
+hipError_t launch_kat_quant(const int16_t* coef, const uint8_t* tq, int16_t* quant,
+                            int16_t* dequant, int count, hipStream_t s);
 
 }  // namespace cairo

@@ -10,6 +10,7 @@
 //                    reconstruct, left to right                encode.cpp:17-203,
 //                                                              decode.cpp:15-144
 //   k_kat_transform  known-answer entry of the transform chain (tests)
+//   k_kat_quant      known-answer entry of the quantizer alone (tests)
 // (The conversion kernels at its two ends, k_convert_batch and k_yuv_to_rgb,
 // are in pixfmt.hip.)
 //
@@ -3426,6 +3427,30 @@ hipError_t launch_kat_transform(const int16_t* src, const int16_t* pred, int16_t
                                 hipStream_t s) {
   hipLaunchKernelGGL(k_kat_transform, dim3(count), dim3(256), 0, s, src, pred, coef, recon, qtype,
                      qvar);
+  return hipGetLastError();
+}
+
+// KAT: the quantizer alone.  tq[2m] = block type, tq[2m+1] = qp itself; every
+// element through the engine's quant_elem and dequant_elem.
+__global__ __launch_bounds__(256) void k_kat_quant(const int16_t* coef, const uint8_t* tq,
+                                                   int16_t* quant, int16_t* dequant) {
+  load_tables();
+  const int m = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t type = tq[2 * m];
+  const int qp = tq[2 * m + 1];
+  const bool intra_path = (type & kIntra) && !(type & kMotion);
+  const int nblk = wave < 2 ? 2 : 1;
+  for (int bi = 0; bi < nblk; bi++) {
+    const int e = (wave + 4 * bi) * 64 + lane;
+    const int16_t qv = quant_elem(e, coef[(size_t)m * kMBElems + e], qp, intra_path);
+    quant[(size_t)m * kMBElems + e] = qv;
+    dequant[(size_t)m * kMBElems + e] = dequant_elem(e, qv, qp, intra_path);
+  }
+}
+
+hipError_t launch_kat_quant(const int16_t* coef, const uint8_t* tq, int16_t* quant,
+                            int16_t* dequant, int count, hipStream_t s) {
+  hipLaunchKernelGGL(k_kat_quant, dim3(count), dim3(256), 0, s, coef, tq, quant, dequant);
   return hipGetLastError();
 }
 

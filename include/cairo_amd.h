@@ -79,7 +79,8 @@ extern "C" {
  *      cairo_rate_init, cairo_rate_step, cairo_ctx_set_rate,
  *      cairo_ctx_frame_rate, cairo_stream_frame_rate, cairo_kat_rate_observe.
  *      A context on which cairo_ctx_set_rate was never called behaves as
- *      before. */
+ *      before.
+ *   4  (unchanged) cairo_kat_quant is added. */
 #define CAIRO_AMD_API_VERSION 4
 CAIRO_API int cairo_api_version(void);
 
@@ -867,6 +868,15 @@ CAIRO_API int cairo_kat_rate_observe(const uint32_t *words, uint64_t total_words
 CAIRO_API int cairo_kat_transform(const int16_t *src, const int16_t *pred, const uint8_t *qtype,
                                   int count, int16_t *coef, int16_t *recon, int32_t *qvar,
                                   int device);
+
+/* Known-answer check of the device quantizer and dequantizer alone: count
+ * (>= 1) macroblocks of 384 int16 coefficients in cairo_kat_transform's
+ * layout.  tq[2m] = block type (0..3: a type with the copy bit has no
+ * coefficients and is refused), tq[2m+1] = the quantizer parameter qp itself,
+ * 1..31, not a quality.  Out: every element quantized, and that value
+ * dequantized.  Host buffers in and out. */
+CAIRO_API int cairo_kat_quant(const int16_t *coef, const uint8_t *tq, int count, int16_t *quant,
+                              int16_t *dequant, int device);
 
 /* Known-answer check of the GPU entropy precode (the kernels behind
  * CAIRO_OUT_FEED) on host buffers, without a context or the engine: count
